@@ -15,9 +15,11 @@ of poses").  `--flow k0` measures the explicit one-launch fast mode instead (rou
 it under `k0_fast_mode`.  Weak scaling: every rank owns 1024 objects per step.  The steps
 rotate over --batches DISTINCT resident batches (default 12 x 23.4 MB = 281 MB > the 256 MiB Infinity Cache),
 so the inputs really stream from HBM.  W untimed warm-up steps, then EXACTLY K steps between barrier +
-torch.cuda.synchronize() pairs; the reported time is the MAX over ranks; rank 0 prints ONE JSON line.
+torch.cuda.synchronize() pairs; the reported time is the MAX over ranks; rank 0 prints ONE JSON line, the headline (value,
+ms_per_step = the wall time of one timed step, the variants' values, the checks), and with --details FILE writes the whole record
+there.  --dump-outputs DIR writes what the last timed step computed (headline key `outputs_dumped`).
 
-Extra objects in the line (prompt ④):
+Extra objects in the record (prompt ④):
   roofline      dominant kernel's algorithmic bytes / its average launch duration (HIP events around each
                 launch, on the stream it is launched on), against the 8 TB/s HBM peak; `flops` = counted fp64
                 FLOP per launch (from the kernel's own per-object iteration / inlier counts) against the
@@ -74,7 +76,18 @@ def parse():
     ap.add_argument('--workload', choices=['config2', 'stress'], default='config2',
                     help="config2 (default, the metric's configuration) or stress = BASELINE config 5's per-GPU shard: 8192 objects x "
                          '56x56 correspondences, fp16 storage (a parity-test shape; an extra line, never the judged one)')
-    return ap.parse_args()
+    ap.add_argument('--details', metavar='FILE', default=None,
+                    help='write the whole record (configuration, rooflines, variants, secondary figures, CPU baselines) to FILE as one JSON '
+                         'line; stdout carries the headline line only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed — the launch outputs a caller receives: valid, pose, cov, '
+                         'tr, inlier_mask (+ all_ranks_* from the all-gather when N > 1) — as DIR/<name>.npy in float32, at most 64 MB in all '
+                         '(beyond that a fixed seeded sample of inlier_mask rows, their indices in inlier_mask_rows.npy as float64).  Same arguments, same inputs: '
+                         'two builds can be compared output for output')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def host_threads():
@@ -94,6 +107,28 @@ def perturbed_gt_init(batch, seed):
     rng = np.random.default_rng(seed)
     gt = np.concatenate([batch['gt_yaw'][:, None], batch['gt_t']], 1)
     return gt + rng.normal(0.0, 1.0, gt.shape) * np.array([0.1, 0.3, 0.1, 1.0])
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def write_outputs(dirname, arrays, seed=SEED):
+    """--dump-outputs: arrays (name -> numpy array) as DIR/<name>.npy, float64 kept, everything else as float32.  If they exceed
+    DUMP_LIMIT_BYTES together, the largest one (the inlier masks of a large workload) is cut to a fixed seeded sample of its rows
+    and <name>_rows.npy holds their indices.  Returns the names written."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        big = max(arrays, key=lambda k: arrays[k].nbytes)
+        a = arrays[big]
+        row = a.nbytes // a.shape[0]
+        k = (DUMP_LIMIT_BYTES - 64 * 1024 - (total - a.nbytes)) // (row + 8)         # 64 KiB left for the .npy headers
+        rows = np.sort(np.random.default_rng(seed).choice(a.shape[0], k, replace=False))
+        arrays[big], arrays[big + '_rows'] = a[rows], rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    return sorted(arrays)
 
 
 def cpu_baseline(np_inputs, init_pose, seconds, ref_flow=True, workload='config-2 batch 0'):
@@ -167,6 +202,22 @@ def _protect_stdout():
         sys.stdout.flush()
         _JSON_FD = os.dup(1)
         os.dup2(2, 1)
+
+
+HEADLINE_KEYS = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data',
+                 'value_cold', 'value_rotation_normalised', 'valid_fraction', 'outputs_verified', 'speedup_vs_cpu_1thread', 'speedup_vs_cpu_all_cores',
+                 'comm', 'outputs_dumped')
+
+
+def headline(line):
+    """The result line printed on stdout.  The whole record is ~20 KB, more than a log that keeps the end of a run's output holds, so the
+    line carries the headline figures (a few hundred bytes) and --details FILE the record."""
+    h = {k: line[k] for k in HEADLINE_KEYS if k in line}
+    h['flow'] = line['config']['flow'].split(':')[0]
+    for k in ('steady_state', 'single_stream', 'k0_fast_mode', 'cpu_baseline'):
+        if isinstance(line.get(k), dict) and 'value' in line[k]:
+            h['value_' + k] = line[k]['value']
+    return h
 
 
 def _emit(line):
@@ -512,6 +563,22 @@ def run(args):
             gi = sl // G_SEC
             nb = (sl % G_SEC + 1) * row
             gather_ok = bool(torch.equal(gathered_grp[gi][rank * nb:(rank + 1) * nb], gbuf[gi][:nb]))
+    # --dump-outputs: the last timed step's own result slot, copied now (the loops below reuse the slots)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        sl = (main_loop.i - 1) % S
+        out = {'valid': packs[sl].valid, 'pose': packs[sl].pose, 'cov': packs[sl].cov, 'tr': packs[sl].tr, 'inlier_mask': masks[sl]}
+        if use_dist:                             # what every rank receives: the gathered rows of all ranks for this step (rank-major)
+            if main_loop.G == 1:
+                flat = gathered_step[sl].view(world, row)
+            else:
+                nb = (sl % G_SEC + 1) * row
+                flat = gathered_grp[sl // G_SEC][:world * nb].view(world, nb)[:, nb - row:]
+            out.update({'all_ranks_' + k: v for k, v in PackedResults.unpack(flat, world * B_PER_GPU).items()})
+        names = write_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in out.items()})
+        dumped = {'dir': args.dump_outputs, 'files': [n + '.npy' for n in names], 'step': main_loop.i - 1,
+                  'batch_seed': seeds[(main_loop.i - 1 + rot0) % NB], 'flags': fl_main}
     # every slot written inside the timed window holds exactly what an isolated launch of the same batch produces
     outputs_ok = True
     for i in range(max(0, main_loop.i - S), main_loop.i):
@@ -805,23 +872,31 @@ def run(args):
         if comm is not None:
             comm['gathered_rows_verified'] = gather_ok
             line['comm'] = comm
+        if dumped is not None:
+            line['outputs_dumped'] = dumped
         if ref_flow and world == 1 and not args.no_secondary and not stress:
             # the explicit fast mode, measured by the same script in a child process (the parent is idle meanwhile): rounds 1-4's `value`
             import subprocess
+            import tempfile
+            fd, kfile = tempfile.mkstemp(prefix='mr_bench_k0_', suffix='.json')
+            os.close(fd)
             cmd = [sys.executable, os.path.abspath(__file__), '--flow', 'k0', '--steps', str(args.steps), '--warmup', str(args.warmup), '--batches', str(args.batches),
-                   '--in-flight', str(args.in_flight), '--no-cpu-baseline']
+                   '--in-flight', str(args.in_flight), '--no-cpu-baseline', '--details', kfile]
             try:
                 torch.cuda.synchronize()
                 cp = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=dict(os.environ, MR_BENCH_SKIP_EPNP_SECONDARY='1'))
-                kj = json.loads(cp.stdout.decode().strip().splitlines()[-1])
+                with open(kfile) as f:
+                    kj = json.loads(f.read())
                 line['k0_fast_mode'] = {
                     'what': "PnPUncert(initialiser='k0'): this repository's one-launch consensus initialiser fused with the LM — NOT the reference's initialiser "
-                            '(inlier sets differ from the reference flow\'s on ~13 % of config-2 objects); `python bench.py --flow k0` prints this line on its own',
+                            '(inlier sets differ from the reference flow\'s on ~13 % of config-2 objects); `python bench.py --flow k0 --details FILE` writes this record on its own',
                     'value': kj['value'], 'unit': 'solves/s', 'ms_per_step': kj['ms_per_step'], 'steps': kj['steps'], 'steady_state': kj.get('steady_state'),
                     'single_stream': kj.get('single_stream'), 'roofline': kj.get('roofline'), 'config': {k: kj['config'].get(k) for k in ('stages', 'launches_in_flight', 'waves_per_object', 'prewarm')},
                     'secondary_throughput': kj.get('secondary_throughput')}
             except Exception as e:  # noqa: BLE001
                 line['k0_fast_mode'] = {'error': repr(e)}
+            finally:
+                os.remove(kfile)
         if world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(np_batch0, perturbed_gt_init(batch0, SEED) if not stress else None, args.cpu_seconds, ref_flow,
                               'config-2 batch 0' if not stress else 'the stress batch (56x56 correspondences; float32 values, the GPU reads them rounded to fp16)')
@@ -841,7 +916,10 @@ def run(args):
                 line['speedup_epnp_initialiser_vs_cpu_epnp_1thread'] = extra['epnp_initialiser']['value'] / cb['cpu_baseline_epnp']['value']
             if 'init_given' in extra:
                 line['speedup_init_given_vs_cpu_1thread'] = extra['init_given']['value'] / cb['cpu_baseline_init_given']['value']
-        _emit(line)
+        if args.details:
+            with open(args.details, 'w') as f:
+                f.write(json.dumps(line) + '\n')
+        _emit(headline(line))
     if rccl is not None:
         rccl.close()
     if use_dist:

@@ -268,7 +268,7 @@ def test_sharded_pnp_with_the_hip_solve_in_an_nccl_job():
 
 
 @pytest.mark.gpu
-def test_bench_self_launches_its_ranks():
+def test_bench_self_launches_its_ranks(tmp_path):
     """`python bench.py --gpus 2` starts its own two ranks.  On a 1-GPU box RCCL refuses two ranks on one device, so the
     test mode MR_BENCH_OVERSUBSCRIBE=1 shares the GPU and exchanges through gloo — launcher, rank environment, per-rank
     batches, max-over-ranks timing and the JSON line (n_gpus, comm block) are the real code path; without the override the
@@ -282,12 +282,15 @@ def test_bench_self_launches_its_ranks():
         assert r.returncode != 0 and 'needs 2 visible MI355X devices' in r.stderr
         env['MR_BENCH_OVERSUBSCRIBE'] = '1'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2', '--batches', '2',
-                        '--no-cpu-baseline', '--no-secondary'], capture_output=True, text=True, timeout=900, env=env)
+                        '--no-cpu-baseline', '--no-secondary', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1000:], r.stderr[-3000:])
     line = json.loads(lines[0])
     assert line['n_gpus'] == 2 and line['comm']['nranks'] == 2 and line['comm']['bytes_per_rank'] == 88 * 1024
     assert line['comm']['gathered_rows_verified'] is True and line['value'] > 0 and line['scaling'] == 'weak'
+    # rank 0 dumps its own rows and the gathered rows of both ranks (rank-major): its own come first
+    pose, all_pose = np.load(tmp_path / 'pose.npy'), np.load(tmp_path / 'all_ranks_pose.npy')
+    assert all_pose.shape == (2048, 4) and np.array_equal(all_pose[:1024], pose, equal_nan=True)
     assert ('rccl' in line['comm']['backend']) == (ndev >= 2)
 
 
@@ -352,7 +355,7 @@ def test_private_rccl_communicator_through_the_rank_launcher():
 
 
 @pytest.mark.gpu
-def test_bench_rccl_path_with_launch_sets_and_its_fallback():
+def test_bench_rccl_path_with_launch_sets_and_its_fallback(tmp_path):
     """bench.py inside an RCCL job (MR_BENCH_FORCE_DIST=1: the only way to run that path on a 1-GPU box): the default line — the
     reference flow in launch sets of five calls — exchanges every step's packed rows over the private communicator; when that
     communicator cannot be built (MR_RCCL_LIBRARY points nowhere: VERDICT r4 item 7b) the job falls back to torch.distributed's
@@ -363,11 +366,16 @@ def test_bench_rccl_path_with_launch_sets_and_its_fallback():
         env = dict(os.environ, MR_BENCH_FORCE_DIST='1', MASTER_PORT=str(29600 + int(broken)))
         if broken:
             env['MR_RCCL_LIBRARY'] = '/nonexistent/librccl.so'
-        r = subprocess.run(base, capture_output=True, text=True, timeout=900, env=env)
+        details, out = tmp_path / f'details{int(broken)}.json', tmp_path / f'out{int(broken)}'
+        r = subprocess.run(base + ['--details', str(details), '--dump-outputs', str(out)], capture_output=True, text=True, timeout=900, env=env)
         lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
         assert r.returncode == 0 and len(lines) == 1, (r.stdout[-500:], r.stderr[-3000:])
-        d = json.loads(lines[0])
+        d = json.loads(details.read_text())
         c = d['comm']
+        assert json.loads(lines[0])['comm'] == c
+        # the dumped step's rows as the all-gather delivered them (one rank: its own rows)
+        for k in ('pose', 'cov', 'tr', 'valid'):
+            assert np.array_equal(np.load(out / f'all_ranks_{k}.npy'), np.load(out / f'{k}.npy'), equal_nan=True), k
         assert d['config']['flow'].startswith('reference') and d['config']['calls_per_launch_set'] == 5 and d['outputs_verified'] is True
         assert c['nranks'] == 1 and c['bytes_per_rank'] == 88 * 1024 and c['gathered_rows_verified'] is True
         if broken:

@@ -601,18 +601,24 @@ def test_reference_eigenvalue_rule_for_ill_conditioned_hessians(dev, orc):
     assert outs[True][0][6:].sum() >= 16
 
 
-def test_bench_line_describes_the_regime_it_measured():
+def test_bench_line_describes_the_regime_it_measured(tmp_path, dev):
     """bench.py's ONE JSON line: `value` is the REFERENCE's flow (what the drop-in boundary runs) with launch sets
     in flight, the top-level roofline is the timed regime's (chip-level bytes / wall) with the longest launch under `dominant_kernel`,
     `reference_flow` carries one call at a time and the launch split, the explicit fast mode rides under `k0_fast_mode` (a child run of
     `--flow k0`, whose own line keeps rounds 1-4's layout)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '8', '--warmup', '2', '--batches', '4', '--no-cpu-baseline'],
-                       capture_output=True, text=True, timeout=1500)
+    details = tmp_path / 'bench_details.json'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '8', '--warmup', '2', '--batches', '4', '--no-cpu-baseline',
+                        '--details', str(details), '--dump-outputs', str(tmp_path / 'out')], capture_output=True, text=True, timeout=1500)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-500:], r.stderr[-2000:])
-    d = json.loads(lines[0])
+    h = json.loads(lines[0])                                   # the headline line: small enough for the end of a log, the record's figures
+    d = json.loads(details.read_text())
+    assert len(lines[0]) < 2048 and h['steps'] == 8 and h['flow'] == 'reference' and h['outputs_verified'] is True
+    assert all(h[k] == d[k] for k in ('value', 'ms_per_step', 'value_cold', 'value_rotation_normalised', 'valid_fraction'))
+    assert h['value_steady_state'] == d['steady_state']['value'] and h['value_k0_fast_mode'] == d['k0_fast_mode']['value']
+    assert abs(h['ms_per_step'] - 1e3 * 1024 / h['value']) <= 1e-9 * h['ms_per_step']
     assert d['metric'].startswith('PnP solves/sec') and d['unit'] == 'solves/s' and d['dtype'] == 'f64' and d['n_gpus'] == 1 and d['steps'] == 8
     assert d['config']['flow'].startswith('reference') and 1 <= d['config']['calls_per_launch_set'] <= 8 and 'solvePnPRansac' in d['config']['stages']
     rf = d['roofline']
@@ -641,3 +647,14 @@ def test_bench_line_describes_the_regime_it_measured():
     assert k0['value'] > d['value'] and k0['steady_state']['value'] > 0 and k0['single_stream']['value'] > 0
     assert k0['roofline']['kernel'].startswith('pnp_uncert_kernel<float, ') and k0['roofline']['kernel'].endswith('false>')
     assert 'head_to_pose_1024' in k0['secondary_throughput'] and 'epnp_initialiser' not in k0['secondary_throughput']
+    od = h['outputs_dumped']                                   # --dump-outputs: the last timed step's outputs = an isolated launch of its batch
+    from monorun_amd import PnPEpnpLaunch
+    got = {f[:-4]: np.load(tmp_path / 'out' / f) for f in od['files']}
+    assert od['step'] == 7 and sorted(got) == ['cov', 'inlier_mask', 'pose', 'tr', 'valid'] and all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6 and got['inlier_mask'].shape == (1024, 784)
+    x = [_dv(a, dev) for a in syn.pnp_boundary(syn.make_batch(B=1024, hw=28, seed=od['batch_seed']), planar=True)]
+    ref = PnPEpnpLaunch(*x[:6], z_min=0.5, epnp_istd_thres=0.6, epnp_ransac_thres=x[6], inlier_opt_only=True, flags=od['flags'])
+    ref.run()
+    torch.cuda.synchronize()
+    for k in ('valid', 'pose', 'cov', 'tr', 'mask'):
+        assert np.array_equal(got['inlier_mask' if k == 'mask' else k], getattr(ref, k).cpu().numpy().astype(np.float32), equal_nan=True), k

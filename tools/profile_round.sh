@@ -13,8 +13,8 @@ R=$GRAFT_REPO_ROOT
 PARTS=${PARTS:-bench stream1 inflight noc epnp}
 # 1) the bench line (with CPU baselines and secondary figures), exactly as the driver runs it, and the long window
 if [[ " $PARTS " == *" bench "* ]]; then
-python $R/bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
-python $R/bench.py --steps 240 --warmup 24 --no-cpu-baseline --no-secondary > $OUT/bench_240.json 2>> $OUT/bench.err
+python $R/bench.py --steps 20 --warmup 5 --details $OUT/bench.json > $OUT/bench_line.json 2> $OUT/bench.err
+python $R/bench.py --steps 240 --warmup 24 --no-cpu-baseline --no-secondary --details $OUT/bench_240.json >> $OUT/bench_line.json 2>> $OUT/bench.err
 fi
 prof() {   # prof <subdir> <counters or ""> -- <command...>
     local sub=$1 pmc=$2; shift 3
