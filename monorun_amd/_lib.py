@@ -72,6 +72,11 @@ def load():
     lib.mr_pick_waves.restype = i32
     lib.mr_pick_waves.argtypes = [i32, i32]
     lib.mr_spin.argtypes = [i32, vp]
+    # development aids for the tests (not in the public header, not in EXPORTED_SYMBOLS)
+    lib.mr_debug_launch_waves.restype = i32
+    lib.mr_debug_launch_waves.argtypes = [i32, i32, i32, i32, i32]
+    lib.mr_debug_block_sum.restype = i32
+    lib.mr_debug_block_sum.argtypes = [i32, vp, vp, vp]
     lib.mr_pnp_uncert_batched.restype = i32
     lib.mr_pnp_uncert_batched.argtypes = [
         vp, i64p, vp, i64p, vp, i64p, i32,          # x2d, istd, x3d (+strides), in_dtype

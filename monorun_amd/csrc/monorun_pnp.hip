@@ -925,6 +925,9 @@ int launch_ext(const PnpArgs &a, hipStream_t st, const PnpCallTable *tbl = nullp
     return MR_OK;
 }
 
+// the instantiations of the external-initialiser launch (launch_ext): 2, 4 or 8 waves per object
+int ext_wpo(int wpo) { return wpo < 2 ? 2 : (wpo == 3 ? 4 : wpo); }
+
 template <typename T>
 int launch_wpo(PnpArgs &a, int wpo, hipStream_t st, const PnpCallTable *tbl = nullptr, const EpnpRefitIn *rf = nullptr) {
     a.elem_size = (int)sizeof(T);
@@ -933,8 +936,7 @@ int launch_wpo(PnpArgs &a, int wpo, hipStream_t st, const PnpCallTable *tbl = nu
     a.nla = a.plan.n_leaves > 0 ? a.plan.n_leaves : 1;
     { const int mi = (a.flags & MR_LM_MAXIT_MASK) >> MR_LM_MAXIT_SHIFT; a.lm_max_iter = mi ? mi : 50; }
     if (a.init_mask) {                      // external initialiser: 2, 4 or 8 waves per object
-        if (wpo < 2) wpo = 2;
-        if (wpo == 3) wpo = 4;
+        wpo = ext_wpo(wpo);
         switch (wpo) {
             case 2: return launch_ext<T, 2>(a, st, tbl, rf);
             case 4: return launch_ext<T, 4>(a, st, tbl, rf);
@@ -977,6 +979,28 @@ int widen_for_large_tiles(int wpo, const PnpArgs &a, int flags, int in_dtype) {
     PnpArgs t = a;
     t.elem_size = (in_dtype == MR_F16) ? 2 : 4;                 // the launcher sets it later, from the template type
     return (lds_bytes(t, 4) * 3 > dev_info().lds_per_cu) ? 8 : wpo;
+}
+
+// Waves per object of the LM / covariance launch of pnp_uncert_launch: the size rule, widened for large tiles, and with an external
+// initialiser (a.init_mask: the default flow) the nearest instantiation launch_ext has.  The covariance stage's summation tree follows
+// this count; mr_debug_launch_waves answers with this same function, so what the tests ask for is what the launch uses.
+int lm_launch_waves(const PnpArgs &a, int flags, int in_dtype) {
+    const int w = widen_for_large_tiles(pick_wpo(a.B, a.P, flags), a, flags, in_dtype);
+    return a.init_mask ? ext_wpo(w) : w;
+}
+
+// development aid for the tests (mr_debug_block_sum): block_sum_packed<WPO, 10> — the covariance stage's reduction — on caller-supplied
+// per-lane partials (64 WPO lanes x 10), one workgroup; lanes 0..9 of every wave write their totals to out[wave * 10 + k]
+template <int WPO>
+__global__ void __launch_bounds__(64 * WPO) block_sum_probe_kernel(const double *part, double *out) {
+    __shared__ double red[2 * WPO * kRedN];
+    double acc[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) acc[k] = part[threadIdx.x * 10 + k];
+    int flip = 0;
+    const double t = block_sum_packed<WPO, 10>(acc, red, flip);
+    const int lane = threadIdx.x & 63;
+    if (lane < 10) out[(threadIdx.x >> 6) * 10 + lane] = t;
 }
 
 // 6-DoF refinement (second launch of pnp_uncert(..., use_6dof=True)): see pnp6_kernel.inc
@@ -1170,6 +1194,35 @@ int mr_pick_waves(int objects_in_flight, int P) {
     return pick_wpo(objects_in_flight, P, 0);
 }
 
+// development aids for the tests (not in the public header):
+// waves per object of the LM / covariance launch over `objects` objects x P points of `in_dtype` with `flags` (MR_WAVES bits honoured),
+// after the default flow's initialiser when `after_init` is set (mr_pnp_uncert_from_init_* / _from_epnp_grouped), else the fast mode's
+int mr_debug_launch_waves(int objects, int P, int in_dtype, int flags, int after_init) {
+    if (objects < 1 || P < 4 || P > 64 * kMaxChunks || (in_dtype != MR_F32 && in_dtype != MR_F16 && in_dtype != MR_F64)) return MR_ERR_BAD_ARGUMENT;
+    static const uint8_t any_mask = 0;
+    PnpArgs a;
+    memset(&a, 0, sizeof a);
+    a.B = objects; a.P = P; a.flags = flags;
+    a.init_mask = after_init ? &any_mask : nullptr;
+    return lm_launch_waves(a, flags, in_dtype);
+}
+
+// block_sum_packed<wpo, 10> on `partials` (device, 64 wpo x 10 doubles, lane-major) -> `out` (device, wpo x 10: every wave's totals)
+int mr_debug_block_sum(int wpo, const double *partials, double *out, void *stream) {
+    if (!partials || !out) return MR_ERR_BAD_ARGUMENT;
+    hipStream_t st = (hipStream_t)stream;
+    switch (wpo) {
+        case 1: hipLaunchKernelGGL(block_sum_probe_kernel<1>, dim3(1), dim3(64), 0, st, partials, out); break;
+        case 2: hipLaunchKernelGGL(block_sum_probe_kernel<2>, dim3(1), dim3(128), 0, st, partials, out); break;
+        case 3: hipLaunchKernelGGL(block_sum_probe_kernel<3>, dim3(1), dim3(192), 0, st, partials, out); break;
+        case 4: hipLaunchKernelGGL(block_sum_probe_kernel<4>, dim3(1), dim3(256), 0, st, partials, out); break;
+        case 8: hipLaunchKernelGGL(block_sum_probe_kernel<8>, dim3(1), dim3(512), 0, st, partials, out); break;
+        default: return MR_ERR_BAD_ARGUMENT;
+    }
+    HIP_TRY(hipGetLastError());
+    return MR_OK;
+}
+
 int mr_pnp_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1214,7 +1267,7 @@ static int pnp_uncert_launch(
         tbl.ncalls = ncalls; a.B = B * ncalls;
         for (int c = 0; c < ncalls; ++c) tbl.call[c] = calls[c];
     }
-    const int wpo = widen_for_large_tiles(pick_wpo(a.B, P, flags), a, flags, in_dtype);
+    const int wpo = lm_launch_waves(a, flags, in_dtype);
     hipStream_t st = (hipStream_t)stream;
     const PnpCallTable *tp = (ncalls > 1 || rf) ? &tbl : nullptr;
     switch (in_dtype) {
@@ -1603,7 +1656,7 @@ int mr_pnp_from_head_batched(
     if (mm == MR_MEAN_PAIRWISE && !(flags & MR_NO_ISTD_MASK)) {
         if (!build_plan(a.plan, P)) return MR_ERR_UNSUPPORTED;
     }
-    return launch_wpo<float>(a, widen_for_large_tiles(pick_wpo(B, P, flags), a, flags, MR_F32), (hipStream_t)stream);
+    return launch_wpo<float>(a, lm_launch_waves(a, flags, MR_F32), (hipStream_t)stream);
 }
 
 int mr_roi_align_avg(const float *input, const float *rois, int K, int C, int H, int W, int out_h, int out_w,

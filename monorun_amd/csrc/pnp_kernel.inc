@@ -392,6 +392,9 @@ __device__ __forceinline__ void chol4_solve(const Chol4 &c, const double (&b)[4]
 }
 
 // Same reduction, but the totals stay lane-distributed: lane k (< N) of EVERY wave returns total k, the other lanes 0.
+// Its tree (butterfly strides 32, 16, 1, 2, 4, 8 within a wave, then the waves in order) is part of the covariance stage's
+// specification: oracle/pnp_oracle.c orc_tree_sum restates it, and tests/test_gpu_launch_regimes.py pins this function to that
+// restatement bit for bit for 1, 2, 3, 4 and 8 waves (mr_debug_block_sum).
 // The LM keeps its 14 sums in this one VGPR pair and pulls scalars out with v_readlane where it needs them, instead of
 // holding 2 x 15 wave-uniform doubles in SGPRs across the evaluation (they did not fit and spilled).
 template <int WPO, int N>

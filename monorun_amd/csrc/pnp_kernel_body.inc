@@ -573,7 +573,8 @@
             // ascending order, each wave's 64 partials combine by the butterfly (strides 32, 16, 1, 2, 4, 8), the waves' totals add up in wave
             // order — so that the Hessian, hence its Cholesky factorisation and the `valid` flag, are the same bits on both sides also
             // where J^T J is singular to rounding (planar / collinear objects: VERDICT r5 weak 1).  The tree depends on WPO: the
-            // restatement takes the wave count (orc.set_cov_waves; 4 is what the library launches for fewer than 2048 objects).
+            // restatement takes the wave count (oracle u2d_pnp(cov_waves=)): the launch's own, which depends on the objects in flight, P,
+            // the storage type and the flow (lm_launch_waves; the tests read it with mr_debug_launch_waves).
 #pragma clang fp contract(off)
             const double yaw = (double)posef[0], tx = (double)posef[1], ty = (double)posef[2], tz = (double)posef[3];
             double sn, cs;

@@ -201,12 +201,22 @@ def istd_inlier_mask(coords_2d_istd, epnp_istd_thres):
 
 def u2d_pnp(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min=0.5,
             epnp_istd_thres=1.0, epnp_ransac_thres=None, inlier_opt_only=False,
-            init_pose=None, n_hyp=32, num_threads=1, return_diag=False, init_mode=0, return_init=False, return_pose64=False):
+            init_pose=None, n_hyp=32, num_threads=1, return_diag=False, init_mode=0, return_init=False, return_pose64=False, cov_waves=None):
     """R4+R5+R6 for a batch (the numpy-level driver).  Returns the reference's 6-tuple
     (ret_val, yaw, t_vec, pose_cov, tr_radius, inlier_mask) [+ diag] [+ init (B,4) fp64]; pose_cov is the
     torch-semantics inverse(J^T J) that pnp_uncert.py:71-85 computes.
     init_mode 0: K0 (this repo's consensus initialiser, what the HIP kernel runs); 1: the reference's own initialiser
-    restated (EPnP inside OpenCV's RANSAC loop, oracle/epnp.inc)."""
+    restated (EPnP inside OpenCV's RANSAC loop, oracle/epnp.inc).
+    cov_waves: the summation tree of the covariance Hessian for this call (the launch's waves per object, 1..8, or 0 = sequential); None
+    keeps the process-wide setting (set_cov_waves, default 4)."""
+    if cov_waves is not None:
+        prev = lib().orc_get_cov_waves()
+        lib().orc_set_cov_waves(ctypes.c_int(int(cov_waves)))
+        try:
+            return u2d_pnp(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min, epnp_istd_thres, epnp_ransac_thres,
+                           inlier_opt_only, init_pose, n_hyp, num_threads, return_diag, init_mode, return_init, return_pose64)
+        finally:
+            lib().orc_set_cov_waves(ctypes.c_int(prev))
     B, P = coords_2d.shape[:2]
     if B == 0:
         out = (np.zeros((0,), bool), np.zeros((0, 1), np.float32), np.zeros((0, 3), np.float32),
@@ -320,9 +330,10 @@ def set_epnp_refit_f64(on):
 
 
 def set_cov_waves(waves):
-    """Summation tree of the covariance Hessian in u2d_pnp / u2d_pnp_epnp: the kernel's for `waves` waves per object (default 4 = what
-    the library launches for fewer than 2048 objects; 2 beyond; mr_pick_waves) — orc_cov_hessian_spec —, or 0 = sequential over the
-    points (rounds 1-5; orc_torch_jacobian)."""
+    """Process-wide summation tree of the covariance Hessian in u2d_pnp / u2d_pnp_epnp: the kernel's for `waves` waves per object
+    (default 4) — orc_cov_hessian_spec —, or 0 = sequential over the points (rounds 1-5; orc_torch_jacobian).  The library's count
+    depends on the launch (objects in flight, P, storage type, flow: mr_debug_launch_waves); a comparison with one launch passes
+    that count per call (u2d_pnp(cov_waves=))."""
     lib().orc_set_cov_waves(ctypes.c_int(int(waves)))
 
 
@@ -335,6 +346,15 @@ def cov_hessian_spec(K, z_min, u_range, v_range, yaw, t, x3d, istd, inlier, wave
     lib().orc_cov_hessian_spec(_p(K, c_dp), ctypes.c_double(z_min), _p(ur, c_dp), _p(vr, c_dp), ctypes.c_double(float(yaw)), _p(t, c_dp), _p(x3d, c_dp), _p(istd, c_dp),
                                _p(m, c_u8p) if m is not None else None, ctypes.c_int(x3d.shape[0]), ctypes.c_int(int(waves)), _p(H, c_dp))
     return H
+
+
+def tree_sum(part, waves):
+    """The covariance stage's reduction (orc_tree_sum = the kernel's block_sum_packed): part (64 waves, n) per-thread partials -> (n,)."""
+    part = _d(part)
+    assert part.ndim == 2 and part.shape[0] == 64 * int(waves)
+    out = np.zeros(part.shape[1])
+    lib().orc_tree_sum(_p(part, c_dp), ctypes.c_int(int(waves)), ctypes.c_int(part.shape[1]), _p(out, c_dp))
+    return out
 
 
 def spec_sincos(x):

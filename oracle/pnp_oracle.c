@@ -607,7 +607,8 @@ void orc_torch_jacobian(const double *K /*9*/, double z_min, const double *u_ran
  *     accumulates inliers t, t + 64 waves, ... in ascending order (q-th inlier = q-th set bit of the mask) with
  *     acc = fma(Ju_i, Ju_j, fma(Jv_i, Jv_j, acc)); the 64 partials of a wave combine by the butterfly with strides 32, 16, 1, 2, 4, 8
  *     (v_permlane32_swap, v_permlane16_swap, four DPP steps: epnp_tree64), the waves' totals add up in wave order.
- * waves = the kernel's waves per object (4 for launches of fewer than 2048 objects, 2 beyond; mr_pick_waves), 1..8.
+ * waves = the kernel's waves per object, 1..8: what the launch picks by the objects in flight, P, the storage type and the flow
+ * (csrc/monorun_pnp.hip lm_launch_waves, queried by the tests through mr_debug_launch_waves).
  * ---------------------------------------------------------------------------------------- */
 static void orc_spec_sincos(double x, double *sn, double *cs) {
     const double kd = rint(x * 6.36619772367581382433e-01);
@@ -644,6 +645,21 @@ static double orc_tree64(double *p /* [64], destroyed */) {            /* = epnp
     double q[64];
     for (int t = 0; t < 6; ++t) { for (int l = 0; l < 64; ++l) q[l] = p[l] + p[l ^ stride[t]]; memcpy(p, q, sizeof q); }
     return p[0];
+}
+
+/* The covariance stage's reduction (csrc/pnp_kernel.inc block_sum_packed) of n sums: part[(64 waves) x n] per-thread partials, thread-major;
+ * each wave's 64 partials by orc_tree64, the waves' totals added in wave order. */
+void orc_tree_sum(const double *part, int waves, int n, double *out) {
+    for (int q = 0; q < n; ++q) {
+        double acc = 0.0;
+        for (int w = 0; w < waves; ++w) {
+            double p64[64];
+            for (int l = 0; l < 64; ++l) p64[l] = part[(size_t)(64 * w + l) * n + q];
+            const double ws = orc_tree64(p64);
+            acc = (w == 0) ? ws : acc + ws;
+        }
+        out[q] = acc;
+    }
 }
 
 void orc_cov_hessian_spec(const double *K /*9*/, double z_min, const double *u_range, const double *v_range,
@@ -694,16 +710,7 @@ void orc_cov_hessian_spec(const double *K /*9*/, double z_min, const double *u_r
         for (int a = 0; a < 4; ++a) for (int b = a; b < 4; ++b, ++q) hacc[q] = fma(J[a], J[b], fma(J[4 + a], J[4 + b], hacc[q]));
     }
     double tot[10];
-    for (int q = 0; q < 10; ++q) {
-        double acc = 0.0;
-        for (int w = 0; w < waves; ++w) {
-            double p64[64];
-            for (int l = 0; l < 64; ++l) p64[l] = part[64 * w + l][q];
-            const double ws = orc_tree64(p64);
-            acc = (w == 0) ? ws : acc + ws;
-        }
-        tot[q] = acc;
-    }
+    orc_tree_sum(&part[0][0], waves, 10, tot);
     free(part);
     int q = 0;
     for (int a = 0; a < 4; ++a) for (int b = a; b < 4; ++b, ++q) H[4 * a + b] = H[4 * b + a] = tot[q];
@@ -1089,8 +1096,10 @@ static int orc_epnp_init(const float *x2d, const float *x3d, uint8_t *mask, int 
  * Inputs contiguous float32 (B,P,2),(B,P,2),(B,P,3); K (Kb,9), ranges (Rb,2) broadcast when Kb/Rb==1.
  * mask: in = istd inlier mask from the host (numpy) stage, out = final inlier mask.
  * ---------------------------------------------------------------------------------------- */
-static int orc_cov_waves = 4;   /* waves per object whose summation tree the covariance Hessian follows (orc_cov_hessian_spec); 0 = the sequential order of rounds 1-5 */
+static int orc_cov_waves = 4;   /* waves per object whose summation tree the covariance Hessian follows (orc_cov_hessian_spec; the launch's own count
+                                   depends on the launch: oracle.py u2d_pnp(cov_waves=)); 0 = the sequential order of rounds 1-5 */
 void orc_set_cov_waves(int w) { orc_cov_waves = w < 0 ? 0 : (w > 8 ? 8 : w); }
+int orc_get_cov_waves(void) { return orc_cov_waves; }
 
 static void orc_one_object(const float *x2d, const float *istd, const float *x3d, const float *K,
                            const float *ur, const float *vr, const float *thr, const double *init,

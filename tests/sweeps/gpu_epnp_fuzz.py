@@ -7,8 +7,11 @@ import numpy as np, torch
 from monorun_amd import synthetic as syn
 from monorun_amd.ops.least_squares.pnp_uncert import pnp_uncert_epnp_device
 from oracle import oracle as orc
+from monorun_amd import _lib
+from monorun_amd.ops.least_squares.pnp_uncert import _DTYPES
 from tests import fuzz_cases
 dev = torch.device('cuda:0')
+lib = _lib.load()
 rng = np.random.default_rng(int(os.environ.get('SEED', 0)))
 def dv(a):
     t = torch.from_numpy(np.asarray(a)); d = torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=dev); d.copy_(t); return d
@@ -19,8 +22,9 @@ for trial in range(int(os.environ.get('TRIALS', 40))):
     mode = trial % 10
     x2d, istd, x3d, K, ur, vr, thr = fuzz_cases.make_case(mode, rng)
     B, P = x2d.shape[:2]
+    waves = lib.mr_debug_launch_waves(B, P, _DTYPES[torch.float32], 0, 1)      # the covariance stage's tree is the LM launch's
     with np.errstate(all='ignore'):
-        ref = orc.u2d_pnp_epnp(x2d, istd, x3d, K, ur, vr, 0.5, 0.6, thr, True, return_diag=True, return_init=True, num_threads=0)
+        ref = orc.u2d_pnp_epnp(x2d, istd, x3d, K, ur, vr, 0.5, 0.6, thr, True, return_diag=True, return_init=True, num_threads=0, cov_waves=waves)
     d = [dv(x2d), dv(istd), dv(x3d), dv(K), dv(ur), dv(vr), dv(thr)]
     out = pnp_uncert_epnp_device(d[0], d[1], d[2], d[3], d[4], d[5], z_min=0.5, epnp_istd_thres=0.6, epnp_ransac_thres=d[6], inlier_opt_only=True, with_diag=True)
     ini, iv = out[6], out[7]

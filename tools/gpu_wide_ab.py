@@ -16,7 +16,9 @@ NB = int(os.environ.get('NBATCH', 12))
 for BO in [int(v) for v in os.environ.get('OBJECTS', '100,256,1024').split(',')]:
     batches = [[dv(a) for a in syn.pnp_boundary(syn.make_batch(B=BO, seed=1234 + 7919 * i, outlier_frac=(0.15, 0.4)[i % 2]), planar=True)] for i in range(NB)]
     le = [PnPEpnpLaunch(*b[:6], z_min=0.5, epnp_istd_thres=0.6, epnp_ransac_thres=b[6], inlier_opt_only=True, with_diag=True) for b in batches]
-    for l in le:
+    for l in le:                # zero-filled before the first run: an element no launch writes hashes the same in every process
+        for t in (l.valid, l.pose, l.cov, l.tr, l.mask, l.init_pose, l.init_mask, l.init_valid, l.diag, l.init_diag):
+            t.zero_()
         l.run()
     torch.cuda.synchronize()
     per = []
