@@ -16,10 +16,16 @@ it under `k0_fast_mode`.  Weak scaling: every rank owns 1024 objects per step.  
 rotate over --batches DISTINCT resident batches (default 12 x 23.4 MB = 281 MB > the 256 MiB Infinity Cache),
 so the inputs really stream from HBM.  W untimed warm-up steps, then EXACTLY K steps between barrier +
 torch.cuda.synchronize() pairs; the reported time is the MAX over ranks; rank 0 prints ONE JSON line, the headline (value,
-ms_per_step = the wall time of one timed step, the variants' values, the checks), and with --details FILE writes the whole record
+ms_per_step = the wall time of one timed step; with --full also the variants' values and the checks), and with --details FILE writes the whole record
 there.  --dump-outputs DIR writes what the last timed step computed (headline key `outputs_dumped`).
 
-Extra objects in the record (prompt ④):
+A plain run does what the headline needs and no more: it sets up, runs what has always come before the timed window (the validity
+check, the same window in the state a just-started process finds the GPU in, the pre-conditioning launches), warms up, times the K
+steps, dumps, and prints the line.  `--full` adds everything else after the timed window: the re-check of the timed outputs against
+isolated launches, the variants (rotation-normalised, single stream, steady state, grouped collective), the duration of one collective,
+the per-launch HIP-event figures and the roofline, the secondary figures, the `--flow k0` child run and the CPU baselines.
+
+Extra objects in the record with --full (prompt ④):
   roofline      dominant kernel's algorithmic bytes / its average launch duration (HIP events around each
                 launch, on the stream it is launched on), against the 8 TB/s HBM peak; `flops` = counted fp64
                 FLOP per launch (from the kernel's own per-object iteration / inlier counts) against the
@@ -59,9 +65,12 @@ def parse():
     ap.add_argument('--steps', type=int, default=240)
     ap.add_argument('--warmup', type=int, default=24)
     ap.add_argument('--batches', type=int, default=12, help='distinct resident batches the steps rotate over (12 x 23.4 MB > 256 MiB L3)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary figures (multi-stream, 8192-object launch, per-image latency)')
-    ap.add_argument('--cpu-seconds', type=float, default=20.0, help='target CPU-baseline sample time (all legs together)')
+    ap.add_argument('--full', action='store_true',
+                    help='measure and check everything else after the timed window as well (variants, collective duration, per-launch figures and '
+                         'roofline, output re-check, secondary figures, the --flow k0 child run, CPU baselines); a plain run times the headline only')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary figures (multi-stream, 8192-object launch, per-image latency)')
+    ap.add_argument('--cpu-seconds', type=float, default=20.0, help='with --full: target CPU-baseline sample time (all legs together)')
     ap.add_argument('--waves', type=int, default=0, help='wavefronts per object (0 = library heuristic)')
     ap.add_argument('--in-flight', type=int, default=int(os.environ.get('MR_BENCH_IN_FLIGHT', '4')),
                     help='launches in flight: the steps are issued round-robin on this many HIP streams through monorun_amd.PnPPipeline '
@@ -554,7 +563,7 @@ def run(args):
     main_loop = Loop(L, G_MAIN)
     elapsed = main_loop.timed(args.steps, args.warmup)
     gather_ok = None
-    if use_dist:                                 # the gathered buffer holds every rank's rows (rank-major): check this rank's slice
+    if use_dist and args.full:                   # the gathered buffer holds every rank's rows (rank-major): check this rank's slice
         torch.cuda.synchronize()
         sl = (main_loop.i - 1) % S
         if main_loop.G == 1:
@@ -579,29 +588,30 @@ def run(args):
         names = write_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in out.items()})
         dumped = {'dir': args.dump_outputs, 'files': [n + '.npy' for n in names], 'step': main_loop.i - 1,
                   'batch_seed': seeds[(main_loop.i - 1 + rot0) % NB], 'flags': fl_main}
-    # every slot written inside the timed window holds exactly what an isolated launch of the same batch produces
-    outputs_ok = True
-    for i in range(max(0, main_loop.i - S), main_loop.i):
-        bi, sl = (i + rot0) % NB, i % S
-        ref = (PnPEpnpLaunch if ref_flow else PnPLaunch)(*dev_batches[bi][:6], z_min=0.5, epnp_istd_thres=0.6, epnp_ransac_thres=dev_batches[bi][6], inlier_opt_only=True, flags=fl_main)
-        ref.run()
-        torch.cuda.synchronize()
-        outputs_ok = outputs_ok and bool(torch.equal(ref.pose, packs[sl].pose) and torch.equal(ref.cov, packs[sl].cov) and
-                                         torch.equal(ref.valid, packs[sl].valid) and torch.equal(ref.mask, masks[sl]))
-    assert outputs_ok, 'a pipelined (grouped) launch produced results that differ from an isolated launch of the same batch'
-    # the same loop over a whole number of rotations (the driver's --steps need not be a multiple of --batches, and the batches
-    # take 56 - 98 us each), and on ONE stream (every launch waits for the previous one: what rounds 1 and 2 reported as `value`)
-    variants = {}
-    full = ((args.steps + NB - 1) // NB) * NB
-    variants['rotation_normalised'] = {'steps': full, 'elapsed': Loop(L, G_MAIN).timed(full, min(args.warmup, NB))}
-    if L != 1:
-        variants['single_stream'] = {'steps': full, 'elapsed': Loop(1, G_MAIN).timed(full, min(args.warmup, NB))}
-    if use_dist and rccl is not None:
-        variants['grouped_collective'] = {'steps': full, 'elapsed': Loop(L, G_SEC if G_MAIN == 1 else 1).timed(full, min(args.warmup, NB)),
-                                          'steps_per_collective': G_SEC if G_MAIN == 1 else 1}
-    # steady state: the same loop over >= 240 steps (the driver's 20-step window carries ~10 % of pipeline fill and drain)
-    ss_steps = ((max(240, args.steps) + NB - 1) // NB) * NB
-    variants['steady_state'] = {'steps': ss_steps, 'elapsed': Loop(L, G_MAIN).timed(ss_steps, min(args.warmup, NB))}
+    outputs_ok, variants = None, {}
+    if args.full:
+        # every slot written inside the timed window holds exactly what an isolated launch of the same batch produces
+        outputs_ok = True
+        for i in range(max(0, main_loop.i - S), main_loop.i):
+            bi, sl = (i + rot0) % NB, i % S
+            ref = (PnPEpnpLaunch if ref_flow else PnPLaunch)(*dev_batches[bi][:6], z_min=0.5, epnp_istd_thres=0.6, epnp_ransac_thres=dev_batches[bi][6], inlier_opt_only=True, flags=fl_main)
+            ref.run()
+            torch.cuda.synchronize()
+            outputs_ok = outputs_ok and bool(torch.equal(ref.pose, packs[sl].pose) and torch.equal(ref.cov, packs[sl].cov) and
+                                             torch.equal(ref.valid, packs[sl].valid) and torch.equal(ref.mask, masks[sl]))
+        assert outputs_ok, 'a pipelined (grouped) launch produced results that differ from an isolated launch of the same batch'
+        # the same loop over a whole number of rotations (the driver's --steps need not be a multiple of --batches, and the batches
+        # take 56 - 98 us each), and on ONE stream (every launch waits for the previous one: what rounds 1 and 2 reported as `value`)
+        rot_steps = ((args.steps + NB - 1) // NB) * NB
+        variants['rotation_normalised'] = {'steps': rot_steps, 'elapsed': Loop(L, G_MAIN).timed(rot_steps, min(args.warmup, NB))}
+        if L != 1:
+            variants['single_stream'] = {'steps': rot_steps, 'elapsed': Loop(1, G_MAIN).timed(rot_steps, min(args.warmup, NB))}
+        if use_dist and rccl is not None:
+            variants['grouped_collective'] = {'steps': rot_steps, 'elapsed': Loop(L, G_SEC if G_MAIN == 1 else 1).timed(rot_steps, min(args.warmup, NB)),
+                                              'steps_per_collective': G_SEC if G_MAIN == 1 else 1}
+        # steady state: the same loop over >= 240 steps (the driver's 20-step window carries ~10 % of pipeline fill and drain)
+        ss_steps = ((max(240, args.steps) + NB - 1) // NB) * NB
+        variants['steady_state'] = {'steps': ss_steps, 'elapsed': Loop(L, G_MAIN).timed(ss_steps, min(args.warmup, NB))}
     comm = None
     if use_dist and oversub:
         comm = {'backend': 'gloo (host-staged; MR_BENCH_OVERSUBSCRIBE test mode: several ranks share one GPU, which RCCL refuses)',
@@ -612,7 +622,7 @@ def run(args):
                       (f' — FALLBACK: the private RCCL communicator could not be set up on every rank ({rccl_why}); ~45 us of host time per collective instead of ~5' if rccl_why else '')),
                 'nranks': rccl.nranks() if rccl is not None else dist.get_world_size(),
                 'bytes_per_rank': main_loop.G * row, 'steps_per_collective': main_loop.G, 'result_slots': S}
-        if rccl is not None:
+        if rccl is not None and args.full:
             # duration of the collective itself: timing events on the side stream around isolated all-gathers of one step's rows
             e0 = [torch.cuda.Event(enable_timing=True) for _ in range(20)]
             e1 = [torch.cuda.Event(enable_timing=True) for _ in range(20)]
@@ -628,47 +638,48 @@ def run(args):
             comm['algbw_definition'] = 'bytes every rank ends up with (nranks x bytes_per_rank at 1 step per collective) / median duration of an isolated collective'
     main_loop = None
 
-    # dominant-kernel duration: HIP events around each launch on the launch stream (torch's current stream), rotating batches
-    n_ev = min(max(args.steps, NB), 240)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
-    torch.cuda.synchronize()
-    for i in range(3):                                  # untimed: the first launches after an idle period run at reduced clocks (2 x the time), which a
-        launches_one[(NB - 3 + i) % NB][0].run()        # 20-launch average would carry; the rocprofv3 average this figure is checked against has hundreds
-    for i, (e0, e1) in enumerate(evs):
-        e0.record()
-        launches_one[i % NB][0].run()
-        e1.record()
-    torch.cuda.synchronize()
-    k_ms = np.array([e0.elapsed_time(e1) for e0, e1 in evs])
-    kernel_ms = float(k_ms.mean())
-    per_batch_ms = [float(k_ms[bi::NB].mean()) for bi in range(NB)]
-
-    # ... and of the timed regime's own launches: HIP events on the PIPELINE's streams (the streams these kernels are launched on)
-    # around every launch of a 240-step run of the timed loop's issue pattern.  The launches overlap, so this is the time a launch is
-    # resident, not what it costs the chip: the chip-level rate is value x bytes.
     k_fl_ms = None
-    if L > 1 and not use_dist and not ref_flow:
-        pp = pipe_of(L_ASKED)
-        nfl = 240
-        fev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nfl)]
-        for i in range(2 * L):
-            pp.submit(launches[i % NB][i % S], slot=i % S)
-        pp.drain()
-        for i, (e0, e1) in enumerate(fev):
-            st = pp.streams[(i % S) % pp.depth]
-            e0.record(st)
-            launches[i % NB][i % S].run(pp.handles[(i % S) % pp.depth])
-            e1.record(st)
-        pp.drain()
-        k_fl_ms = np.array([e0.elapsed_time(e1) for e0, e1 in fev])
+    if args.full:
+        # dominant-kernel duration: HIP events around each launch on the launch stream (torch's current stream), rotating batches
+        n_ev = min(max(args.steps, NB), 240)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
+        torch.cuda.synchronize()
+        for i in range(3):                                  # untimed: the first launches after an idle period run at reduced clocks (2 x the time), which a
+            launches_one[(NB - 3 + i) % NB][0].run()        # 20-launch average would carry; the rocprofv3 average this figure is checked against has hundreds
+        for i, (e0, e1) in enumerate(evs):
+            e0.record()
+            launches_one[i % NB][0].run()
+            e1.record()
+        torch.cuda.synchronize()
+        k_ms = np.array([e0.elapsed_time(e1) for e0, e1 in evs])
+        kernel_ms = float(k_ms.mean())
+        per_batch_ms = [float(k_ms[bi::NB].mean()) for bi in range(NB)]
+
+        # ... and of the timed regime's own launches: HIP events on the PIPELINE's streams (the streams these kernels are launched on)
+        # around every launch of a 240-step run of the timed loop's issue pattern.  The launches overlap, so this is the time a launch is
+        # resident, not what it costs the chip: the chip-level rate is value x bytes.
+        if L > 1 and not use_dist and not ref_flow:
+            pp = pipe_of(L_ASKED)
+            nfl = 240
+            fev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nfl)]
+            for i in range(2 * L):
+                pp.submit(launches[i % NB][i % S], slot=i % S)
+            pp.drain()
+            for i, (e0, e1) in enumerate(fev):
+                st = pp.streams[(i % S) % pp.depth]
+                e0.record(st)
+                launches[i % NB][i % S].run(pp.handles[(i % S) % pp.depth])
+                e1.record(st)
+            pp.drain()
+            k_fl_ms = np.array([e0.elapsed_time(e1) for e0, e1 in fev])
 
     if not diag_first:
         valid_frac, flops_per_launch, it_hist = diagnose()
 
     extra = {}
-    if world == 1 and not args.no_secondary and not ref_flow:
+    if args.full and world == 1 and not args.no_secondary and not ref_flow:
         extra = secondary(args, torch, syn, PnPLaunch, dev, dev_batches, batch0, np_batch0, NB)
-    if ref_flow and world == 1 and not args.no_secondary and not stress:
+    if args.full and ref_flow and world == 1 and not args.no_secondary and not stress:
         try:
             extra['head_to_pose_1024_reference_flow'] = head_to_pose_reference(torch, syn, dev)
         except Exception as e:                                          # noqa: BLE001 — secondary figure
@@ -680,7 +691,7 @@ def run(args):
             extra['per_image_B100_reference_flow'] = {'error': repr(e)}
     # reference flow: how one call splits into the initialiser's launches and the LM launch (HIP events on the launch stream, every batch)
     split = None
-    if ref_flow:
+    if ref_flow and args.full:
         lib_ = launches_one[0][0].lib
         st_ = torch.cuda.current_stream(dev).cuda_stream
         ev3 = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(2 * NB)]
@@ -697,62 +708,6 @@ def run(args):
     if rank == 0:
         total = B_PER_GPU * world * args.steps
         ms_per_step = elapsed / args.steps * 1e3
-        achieved = BYTES_PER_SOLVE * B_PER_GPU / (kernel_ms * 1e-3) / 1e9
-        traffic, traffic_src, traffic_iso = None, None, None
-        tfile = os.path.join(ROOT, 'profiles', 'traffic.json')   # HBM bytes per launch from the PMC passes (see profiles/README.md)
-        def newest(pattern):                     # the newest committed profile of this name (profiles/rNN_<pattern>), or None
-            import glob
-            c = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_' + pattern)), reverse=True)
-            return c[0] if c else None
-        if ref_flow:
-            tf = newest('epnp_traffic_stress.json' if stress else 'epnp_traffic.json')
-            if tf:
-                try:
-                    tj = json.load(open(tf))
-                    traffic = traffic_iso = tj.get('hbm_bytes_per_call')
-                    traffic_src = (f'profiles/{os.path.basename(tf)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over all launches of one call, one call at a time, committed; '
-                                   f'{tj.get("ratio_traffic_over_algorithmic", 0):.2f} x the algorithmic bytes); replayed, not measured in this run')
-                except Exception:  # noqa: BLE001
-                    traffic = traffic_iso = None
-        elif os.path.exists(tfile) and not stress:
-            try:
-                tj = json.load(open(tfile))
-                traffic_iso = tj.get('hbm_bytes_per_launch')
-                traffic_fl = (tj.get('in_flight_kernel') or {}).get('hbm_bytes_per_launch')
-                traffic = traffic_fl if (L > 1 and traffic_fl) else traffic_iso
-                traffic_src = ('profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, tools/profile_round.sh ' + str(tj.get('tag', '')) + ', committed: ' +
-                               ('the 2-waves-per-object kernel the timed region launches, counted on isolated launches of it' if (L > 1 and traffic_fl) else 'the isolated-launch kernel') +
-                               '); replayed, not measured in this run')
-            except Exception:  # noqa: BLE001
-                traffic = None
-        valu = None
-        if ref_flow and not stress:
-            vf = newest('epnp_valu_per_launch.json')
-            if vf:
-                try:
-                    vj = json.load(open(vf))
-                    cnt = float(vj['valu_insts_per_call'])
-                    t_min = cnt * 4.0 / (1024 * 2.4e9)
-                    valu = {'valu_insts_per_call': cnt, 'min_issue_time_us_at_4_cycles': t_min * 1e6, 'frac_of_call_time': t_min / (kernel_ms * 1e-3),
-                            'per_launch': vj.get('per_launch'),
-                            'source': f'profiles/{os.path.basename(vf)} (rocprofv3 --pmc SQ_INSTS_VALU over the launches of one call, one call at a time, committed); replayed, not measured in this run'}
-                except Exception:  # noqa: BLE001
-                    valu = None
-        for sname in ('r04_summary.json', 'r03_summary.json', 'r02_summary.json', 'r01_summary.json'):           # PMC instruction counts of the same command
-            sfile = os.path.join(ROOT, 'profiles', sname)
-            if os.path.exists(sfile) and not stress and not ref_flow:
-                try:
-                    sj = json.load(open(sfile))
-                    cnt = (sj['single_stream'] if 'single_stream' in sj else sj)['counters']['SQ_INSTS_VALU']['mean']      # the isolated (4-wave) kernel
-                    # every VALU wave-instruction occupies its SIMD for >= 2 (fp32) .. 4 (fp64) cycles; 1024 SIMDs at 2.4 GHz
-                    t_min = cnt * 4.0 / (1024 * 2.4e9)
-                    valu = {'valu_insts_per_launch': cnt, 'min_issue_time_us_at_4_cycles': t_min * 1e6,
-                            'frac_of_kernel_time': t_min / (kernel_ms * 1e-3),
-                            'source': f'profiles/{sname} (rocprofv3 --pmc SQ_INSTS_VALU, committed); replayed, not measured in this run'}
-                    break
-                except Exception:  # noqa: BLE001
-                    valu = None
-        flops_ach = flops_per_launch / (kernel_ms * 1e-3) / 1e12
         line = {
             'metric': 'PnP solves/sec (1024 proposals, 28x28 corr.)' if not stress else 'PnP solves/sec (stress: 8192 proposals/GPU, 56x56 corr., fp16 storage)', 'value': total / elapsed, 'unit': 'solves/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step,
@@ -776,112 +731,170 @@ def run(args):
                        'issue': ((f'steps issued on {L} HIP streams by monorun_amd.PnPPipeline, {LG} consecutive steps per launch set (monorun_amd.PnPEpnpGroupLaunch: the '
                                   "every launch of the set — the initialiser's six and the re-fit / LM / covariance launch: seven — carries the objects of the set's calls, every call keeps its own input tensors and result buffers); "
                                   if LG > 1 else f'steps issued round-robin on {L} HIP streams by monorun_amd.PnPPipeline (one completion event per result buffer); ') +
-                                 f'every step is one full {B_PER_GPU}-object call into its own buffers, all outputs complete inside the timed window '
-                                 'and verified bit-identical to isolated calls after it') if L > 1 else 'one stream: every launch waits for the previous one',
+                                 f'every step is one full {B_PER_GPU}-object call into its own buffers, all outputs complete inside the timed window' +
+                                 (' and verified bit-identical to isolated calls after it' if args.full else '')) if L > 1 else 'one stream: every launch waits for the previous one',
                        'prewarm': dict(prewarm, what='untimed launches of the same hot path before the W warm-up steps, so that the timed window does not start on idle clocks (MR_BENCH_PREWARM_LAUNCHES=0 disables)'),
                        'parallelism': f'objects sharded x{world}' + (f', 1 all-gather of 88 B/object x {comm["steps_per_collective"]} step(s) per collective' if (world > 1 and comm) else '')},
-            'roofline': {'bound': 'hbm', 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         # filled in below: `achieved` / `frac` describe the TIMED REGIME (the kernel instantiation and issue pattern `value` was measured on)
-                         'achieved': None, 'frac': None,
-                         'kernel': (f'reference flow, ' + LAUNCHES_TEXT + f' (epnp_front / epnp_hyp / epnp_consensus / second round: epnp_round2 or epnp_hyp + epnp_consensus / epnp_refit_betas / pnp_uncert_refit_kernel<{"__half" if stress else "float"}, {((fl_main >> 8) & 15) or 4}>); longest: the last one (re-fit prologue + LM + covariance)' if ref_flow else
-                                    (f'pnp_uncert_kernel<float, {((fl_main >> 8) & 15) or 4}, false>' if not stress else f'pnp_uncert_kernel<__half, {((fl_main >> 8) & 15) or "auto"}, false>')),
-                         'launches_in_flight': L,
-                         'traffic': traffic, 'traffic_source': traffic_src,
-                         'algorithmic_bytes_per_launch': BYTES_PER_SOLVE * B_PER_GPU,
-                         'isolated_launch': {
-                             'achieved': achieved, 'frac': achieved / HBM_PEAK_GBS, 'unit': 'GB/s',
-                             'kernel': ('one whole call of the reference flow (its 6 launches back to back on one stream)' if ref_flow else
-                                        (f'pnp_uncert_kernel<float, {((fl_one >> 8) & 15) or 4}, false>' if not stress else 'pnp_uncert_kernel<__half, auto, false>')),
-                             'kernel_ms_avg': kernel_ms, 'kernel_ms_min': float(k_ms.min()),
-                             'kernel_ms_median': float(np.median(k_ms)), 'kernel_ms_p95': float(np.percentile(k_ms, 95)), 'kernel_ms_per_batch': per_batch_ms,
-                             'measured_on': 'HIP events around ISOLATED launches on one stream (the library\'s own choice there: 4 waves per object), rotating over the '
-                                            'batches, in this run; rocprofv3 of `bench.py --in-flight 1` agrees (profiles/rNN_kernel_stats.csv).  NOT the instantiation the '
-                                            'timed region launches when launches_in_flight > 1',
-                             'batch0_only': {'kernel_ms': per_batch_ms[0], 'frac': BYTES_PER_SOLVE * B_PER_GPU / (per_batch_ms[0] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                             'note': 'batch 0 (the config seed) alone; a launch lasts as long as its slowest object, so batches differ'},
-                             'traffic': traffic_iso, 'valu_issue': valu},
-                         'flops': {'fp64_flop_per_launch': flops_per_launch, 'achieved_tflops': flops_ach, 'peak_tflops': FP64_VECTOR_PEAK_TFLOPS,
-                                   'frac_of_fp64_vector_peak': flops_ach / FP64_VECTOR_PEAK_TFLOPS,
-                                   'model': f'{FLOP_PER_POINT_EVAL} FLOP x inlier points x (LM iterations + 2) per object (SURVEY 8d; iterations and inlier '
-                                            'counts read back from the kernel in this run); K0 and the mask are not counted; rate per ISOLATED launch',
-                                   'lm_iteration_histogram': {str(k): it_hist[k] for k in sorted(it_hist)}},
-                         'note': ('formally HBM-bound (three of the launches stream the object\'s rows once each); in practice the stages are serial fp64 latency chains per object one call at a time, '
-                                  'and issue slots x workgroup residency with launch sets in flight (wave-instruction counts per launch: `isolated_launch.valu_issue`, DESIGN.md section 3)' if ref_flow else
-                                  'formally HBM-bound (read-once streaming); in practice VALU/latency-bound: the tile is LDS-resident across all LM iterations (DESIGN.md)')},
             'value_cold': prewarm.get('window_before', {}).get('value'),      # the same window in a just-started process (before the reported pre-conditioning): compare THIS with rounds 1-3
             'valid_fraction': valid_frac,
-            'outputs_verified': outputs_ok,
-            'secondary_throughput': extra,
         }
-        def per_s(v):
-            return {'value': B_PER_GPU * world * v['steps'] / v['elapsed'], 'unit': 'solves/s', 'ms_per_step': v['elapsed'] / v['steps'] * 1e3, 'steps': v['steps']}
-        rn = per_s(variants['rotation_normalised'])
-        line['value_rotation_normalised'] = rn['value']
-        line['rotation_normalised'] = dict(rn, what=f'the same loop timed over {rn["steps"]} steps = a whole number of rotations over the {NB} batches '
-                                                    '(--steps need not be a multiple of --batches, and the batches take different times)')
-        if 'single_stream' in variants:
-            line['single_stream'] = dict(per_s(variants['single_stream']), what=('ONE CALL AT A TIME: the same steps on one stream, every call (its 6 launches) waits for the previous one'
-                                         if ref_flow else 'the same steps on ONE stream (launches_in_flight = 1): every launch '
-                                         'waits for the previous one and so pays its slowest object; what rounds 1-2 reported as `value`'))
-        if 'grouped_collective' in variants:
-            extra['grouped_collective'] = dict(per_s(variants['grouped_collective']), steps_per_collective=variants['grouped_collective']['steps_per_collective'],
-                                               what='the same loop with the other exchange granularity (one all-gather per this many steps)')
-        chip = line['value'] / world * BYTES_PER_SOLVE / 1e9          # per GPU: algorithmic bytes of all launches / wall time of the timed region
-        line['roofline']['achieved'], line['roofline']['frac'] = chip, chip / HBM_PEAK_GBS
-        line['roofline']['measured_on'] = (
-            f'the timed region itself: algorithmic bytes of its {args.steps} launches / its wall time, per GPU ({L} launches in flight on '
-            f'{L} HIP streams, {((fl_main >> 8) & 15) or 4} waves per object) — launches overlap, so the chip-level rate is what a roofline fraction '
-            'can mean here; per-launch figures of an isolated launch are under `isolated_launch`') if L > 1 else \
-            'one launch at a time: algorithmic bytes / wall time of the timed region (per-launch HIP-event figures under `isolated_launch`)'
-        if k_fl_ms is not None:
-            line['roofline']['launch_resident_ms_in_flight'] = {
-                'avg': float(k_fl_ms.mean()), 'median': float(np.median(k_fl_ms)), 'min': float(k_fl_ms.min()), 'launches': int(len(k_fl_ms)),
-                'what': 'HIP events on the pipeline\'s own streams around every launch of a 240-step run of the timed issue pattern: how long a launch is '
-                        f'resident while {L} overlap (avg / {L} = chip time per launch); agrees with profiles/rNN_kernel_stats_in_flight.csv'}
-        ss = per_s(variants['steady_state'])
-        line['steady_state'] = dict(ss, frac=ss['value'] / world * BYTES_PER_SOLVE / 1e9 / HBM_PEAK_GBS,
-                                    what=f'the timed loop over {ss["steps"]} steps (whole rotations): the {args.steps}-step window of `value` carries the fill and drain of the {L}-deep pipeline')
-        if ref_flow:
-            one = per_s(variants['single_stream']) if 'single_stream' in variants else None
-            lm_name = f'pnp_uncert_refit_kernel<{"__half" if stress else "float"}, {((fl_one >> 8) & 15) or ("auto" if stress else 4)}>'
-            line['reference_flow'] = {
-                'what': "`value` IS this flow since round 5: cv2.solvePnPRansac(EPNP, 30 iterations) restated on the GPU, then the LM + covariance — what PnPUncert built from the "
-                        "reference's own config dict runs (INTEGRATION.md section 2); the one-launch K0 path is the explicit fast mode (`k0_fast_mode`)",
-                'in_flight': {'value': line['value'], 'unit': 'solves/s', 'launches_in_flight': L, 'calls_per_launch_set': LG, 'steady_state': ss['value']},
-                'one_call_at_a_time': one, 'launch_split': split,
-                'per_image_B100': extra.pop('per_image_B100_reference_flow', None)}
-            if split is not None:
-                # the longest launch of the call: the LM launch (its length is its slowest object's: up to 35 LM iterations from EPnP starts)
-                ach = BYTES_PER_SOLVE * B_PER_GPU / (split['lm_launch_ms'] * 1e-3) / 1e9
-                line['roofline']['dominant_kernel'] = {'kernel': lm_name, 'avg_launch_ms': split['lm_launch_ms'], 'achieved': ach, 'unit': 'GB/s', 'frac': ach / HBM_PEAK_GBS,
-                                                       'algorithmic_bytes_per_launch': BYTES_PER_SOLVE * B_PER_GPU,
-                                                       'measured_on': "HIP events on the launch stream around ISOLATED launches of the LM kernel (one call at a time; the launch also carries the initialiser's re-fit as its prologue), every batch, in this run"}
-        if isinstance(extra.get('epnp_initialiser'), dict) and 'value' in extra['epnp_initialiser']:
-            ep = extra['epnp_initialiser']
-            line['reference_flow'] = {
-                'what': "the reference's own flow on the GPU — cv2.solvePnPRansac(EPNP, 30 iterations) restated, then the LM + covariance: PnPUncert(initialiser='epnp'); "
-                        "`value` above is the one-launch K0 path, which is NOT the reference's initialiser (INTEGRATION.md section 2)",
-                'value': ep['value'], 'unit': 'solves/s', 'ms_per_step': ep['ms_per_step'], 'issue': ep.get('issue'),
-                'synchronous_call': ep.get('synchronous_call'), 'in_flight': ep.get('in_flight'), 'roofline': ep.get('roofline'),
-                'launch_split_batch0_ms': {'initialiser': ep.get('epnp_ransac_launches_ms_batch0'), 'lm': ep.get('lm_launch_ms_batch0')}}
-        line['roofline']['in_flight'] = {
-            'launches_in_flight': L, 'achieved': line['value'] / world * BYTES_PER_SOLVE / 1e9, 'unit': 'GB/s',
-            'frac': line['value'] / world * BYTES_PER_SOLVE / 1e9 / HBM_PEAK_GBS,
-            'note': 'chip-level rate of the timed region: algorithmic bytes of ALL launches / wall time (launches overlap, so this is not a '
-                    'per-launch duration); `achieved` / `frac` above are per launch, from HIP events around isolated launches on one stream'}
+        if args.full:
+            achieved = BYTES_PER_SOLVE * B_PER_GPU / (kernel_ms * 1e-3) / 1e9
+            traffic, traffic_src, traffic_iso = None, None, None
+            tfile = os.path.join(ROOT, 'profiles', 'traffic.json')   # HBM bytes per launch from the PMC passes (see profiles/README.md)
+            def newest(pattern):                     # the newest committed profile of this name (profiles/rNN_<pattern>), or None
+                import glob
+                c = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r[0-9][0-9]_' + pattern)), reverse=True)
+                return c[0] if c else None
+            if ref_flow:
+                tf = newest('epnp_traffic_stress.json' if stress else 'epnp_traffic.json')
+                if tf:
+                    try:
+                        tj = json.load(open(tf))
+                        traffic = traffic_iso = tj.get('hbm_bytes_per_call')
+                        traffic_src = (f'profiles/{os.path.basename(tf)} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over all launches of one call, one call at a time, committed; '
+                                       f'{tj.get("ratio_traffic_over_algorithmic", 0):.2f} x the algorithmic bytes); replayed, not measured in this run')
+                    except Exception:  # noqa: BLE001
+                        traffic = traffic_iso = None
+            elif os.path.exists(tfile) and not stress:
+                try:
+                    tj = json.load(open(tfile))
+                    traffic_iso = tj.get('hbm_bytes_per_launch')
+                    traffic_fl = (tj.get('in_flight_kernel') or {}).get('hbm_bytes_per_launch')
+                    traffic = traffic_fl if (L > 1 and traffic_fl) else traffic_iso
+                    traffic_src = ('profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, tools/profile_round.sh ' + str(tj.get('tag', '')) + ', committed: ' +
+                                   ('the 2-waves-per-object kernel the timed region launches, counted on isolated launches of it' if (L > 1 and traffic_fl) else 'the isolated-launch kernel') +
+                                   '); replayed, not measured in this run')
+                except Exception:  # noqa: BLE001
+                    traffic = None
+            valu = None
+            if ref_flow and not stress:
+                vf = newest('epnp_valu_per_launch.json')
+                if vf:
+                    try:
+                        vj = json.load(open(vf))
+                        cnt = float(vj['valu_insts_per_call'])
+                        t_min = cnt * 4.0 / (1024 * 2.4e9)
+                        valu = {'valu_insts_per_call': cnt, 'min_issue_time_us_at_4_cycles': t_min * 1e6, 'frac_of_call_time': t_min / (kernel_ms * 1e-3),
+                                'per_launch': vj.get('per_launch'),
+                                'source': f'profiles/{os.path.basename(vf)} (rocprofv3 --pmc SQ_INSTS_VALU over the launches of one call, one call at a time, committed); replayed, not measured in this run'}
+                    except Exception:  # noqa: BLE001
+                        valu = None
+            for sname in ('r04_summary.json', 'r03_summary.json', 'r02_summary.json', 'r01_summary.json'):           # PMC instruction counts of the same command
+                sfile = os.path.join(ROOT, 'profiles', sname)
+                if os.path.exists(sfile) and not stress and not ref_flow:
+                    try:
+                        sj = json.load(open(sfile))
+                        cnt = (sj['single_stream'] if 'single_stream' in sj else sj)['counters']['SQ_INSTS_VALU']['mean']      # the isolated (4-wave) kernel
+                        # every VALU wave-instruction occupies its SIMD for >= 2 (fp32) .. 4 (fp64) cycles; 1024 SIMDs at 2.4 GHz
+                        t_min = cnt * 4.0 / (1024 * 2.4e9)
+                        valu = {'valu_insts_per_launch': cnt, 'min_issue_time_us_at_4_cycles': t_min * 1e6,
+                                'frac_of_kernel_time': t_min / (kernel_ms * 1e-3),
+                                'source': f'profiles/{sname} (rocprofv3 --pmc SQ_INSTS_VALU, committed); replayed, not measured in this run'}
+                        break
+                    except Exception:  # noqa: BLE001
+                        valu = None
+            flops_ach = flops_per_launch / (kernel_ms * 1e-3) / 1e12
+            line['roofline'] = {'bound': 'hbm', 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                                # filled in below: `achieved` / `frac` describe the TIMED REGIME (the kernel instantiation and issue pattern `value` was measured on)
+                                'achieved': None, 'frac': None,
+                                'kernel': (f'reference flow, ' + LAUNCHES_TEXT + f' (epnp_front / epnp_hyp / epnp_consensus / second round: epnp_round2 or epnp_hyp + epnp_consensus / epnp_refit_betas / pnp_uncert_refit_kernel<{"__half" if stress else "float"}, {((fl_main >> 8) & 15) or 4}>); longest: the last one (re-fit prologue + LM + covariance)' if ref_flow else
+                                           (f'pnp_uncert_kernel<float, {((fl_main >> 8) & 15) or 4}, false>' if not stress else f'pnp_uncert_kernel<__half, {((fl_main >> 8) & 15) or "auto"}, false>')),
+                                'launches_in_flight': L,
+                                'traffic': traffic, 'traffic_source': traffic_src,
+                                'algorithmic_bytes_per_launch': BYTES_PER_SOLVE * B_PER_GPU,
+                                'isolated_launch': {
+                                    'achieved': achieved, 'frac': achieved / HBM_PEAK_GBS, 'unit': 'GB/s',
+                                    'kernel': ('one whole call of the reference flow (its 6 launches back to back on one stream)' if ref_flow else
+                                               (f'pnp_uncert_kernel<float, {((fl_one >> 8) & 15) or 4}, false>' if not stress else 'pnp_uncert_kernel<__half, auto, false>')),
+                                    'kernel_ms_avg': kernel_ms, 'kernel_ms_min': float(k_ms.min()),
+                                    'kernel_ms_median': float(np.median(k_ms)), 'kernel_ms_p95': float(np.percentile(k_ms, 95)), 'kernel_ms_per_batch': per_batch_ms,
+                                    'measured_on': 'HIP events around ISOLATED launches on one stream (the library\'s own choice there: 4 waves per object), rotating over the '
+                                                   'batches, in this run; rocprofv3 of `bench.py --in-flight 1` agrees (profiles/rNN_kernel_stats.csv).  NOT the instantiation the '
+                                                   'timed region launches when launches_in_flight > 1',
+                                    'batch0_only': {'kernel_ms': per_batch_ms[0], 'frac': BYTES_PER_SOLVE * B_PER_GPU / (per_batch_ms[0] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                                    'note': 'batch 0 (the config seed) alone; a launch lasts as long as its slowest object, so batches differ'},
+                                    'traffic': traffic_iso, 'valu_issue': valu},
+                                'flops': {'fp64_flop_per_launch': flops_per_launch, 'achieved_tflops': flops_ach, 'peak_tflops': FP64_VECTOR_PEAK_TFLOPS,
+                                          'frac_of_fp64_vector_peak': flops_ach / FP64_VECTOR_PEAK_TFLOPS,
+                                          'model': f'{FLOP_PER_POINT_EVAL} FLOP x inlier points x (LM iterations + 2) per object (SURVEY 8d; iterations and inlier '
+                                                   'counts read back from the kernel in this run); K0 and the mask are not counted; rate per ISOLATED launch',
+                                          'lm_iteration_histogram': {str(k): it_hist[k] for k in sorted(it_hist)}},
+                                'note': ('formally HBM-bound (three of the launches stream the object\'s rows once each); in practice the stages are serial fp64 latency chains per object one call at a time, '
+                                         'and issue slots x workgroup residency with launch sets in flight (wave-instruction counts per launch: `isolated_launch.valu_issue`, DESIGN.md section 3)' if ref_flow else
+                                         'formally HBM-bound (read-once streaming); in practice VALU/latency-bound: the tile is LDS-resident across all LM iterations (DESIGN.md)')}
+            line['outputs_verified'] = outputs_ok
+            line['secondary_throughput'] = extra
+            def per_s(v):
+                return {'value': B_PER_GPU * world * v['steps'] / v['elapsed'], 'unit': 'solves/s', 'ms_per_step': v['elapsed'] / v['steps'] * 1e3, 'steps': v['steps']}
+            rn = per_s(variants['rotation_normalised'])
+            line['value_rotation_normalised'] = rn['value']
+            line['rotation_normalised'] = dict(rn, what=f'the same loop timed over {rn["steps"]} steps = a whole number of rotations over the {NB} batches '
+                                                        '(--steps need not be a multiple of --batches, and the batches take different times)')
+            if 'single_stream' in variants:
+                line['single_stream'] = dict(per_s(variants['single_stream']), what=('ONE CALL AT A TIME: the same steps on one stream, every call (its 6 launches) waits for the previous one'
+                                             if ref_flow else 'the same steps on ONE stream (launches_in_flight = 1): every launch '
+                                             'waits for the previous one and so pays its slowest object; what rounds 1-2 reported as `value`'))
+            if 'grouped_collective' in variants:
+                extra['grouped_collective'] = dict(per_s(variants['grouped_collective']), steps_per_collective=variants['grouped_collective']['steps_per_collective'],
+                                                   what='the same loop with the other exchange granularity (one all-gather per this many steps)')
+            chip = line['value'] / world * BYTES_PER_SOLVE / 1e9          # per GPU: algorithmic bytes of all launches / wall time of the timed region
+            line['roofline']['achieved'], line['roofline']['frac'] = chip, chip / HBM_PEAK_GBS
+            line['roofline']['measured_on'] = (
+                f'the timed region itself: algorithmic bytes of its {args.steps} launches / its wall time, per GPU ({L} launches in flight on '
+                f'{L} HIP streams, {((fl_main >> 8) & 15) or 4} waves per object) — launches overlap, so the chip-level rate is what a roofline fraction '
+                'can mean here; per-launch figures of an isolated launch are under `isolated_launch`') if L > 1 else \
+                'one launch at a time: algorithmic bytes / wall time of the timed region (per-launch HIP-event figures under `isolated_launch`)'
+            if k_fl_ms is not None:
+                line['roofline']['launch_resident_ms_in_flight'] = {
+                    'avg': float(k_fl_ms.mean()), 'median': float(np.median(k_fl_ms)), 'min': float(k_fl_ms.min()), 'launches': int(len(k_fl_ms)),
+                    'what': 'HIP events on the pipeline\'s own streams around every launch of a 240-step run of the timed issue pattern: how long a launch is '
+                            f'resident while {L} overlap (avg / {L} = chip time per launch); agrees with profiles/rNN_kernel_stats_in_flight.csv'}
+            ss = per_s(variants['steady_state'])
+            line['steady_state'] = dict(ss, frac=ss['value'] / world * BYTES_PER_SOLVE / 1e9 / HBM_PEAK_GBS,
+                                        what=f'the timed loop over {ss["steps"]} steps (whole rotations): the {args.steps}-step window of `value` carries the fill and drain of the {L}-deep pipeline')
+            if ref_flow:
+                one = per_s(variants['single_stream']) if 'single_stream' in variants else None
+                lm_name = f'pnp_uncert_refit_kernel<{"__half" if stress else "float"}, {((fl_one >> 8) & 15) or ("auto" if stress else 4)}>'
+                line['reference_flow'] = {
+                    'what': "`value` IS this flow since round 5: cv2.solvePnPRansac(EPNP, 30 iterations) restated on the GPU, then the LM + covariance — what PnPUncert built from the "
+                            "reference's own config dict runs (INTEGRATION.md section 2); the one-launch K0 path is the explicit fast mode (`k0_fast_mode`)",
+                    'in_flight': {'value': line['value'], 'unit': 'solves/s', 'launches_in_flight': L, 'calls_per_launch_set': LG, 'steady_state': ss['value']},
+                    'one_call_at_a_time': one, 'launch_split': split,
+                    'per_image_B100': extra.pop('per_image_B100_reference_flow', None)}
+                if split is not None:
+                    # the longest launch of the call: the LM launch (its length is its slowest object's: up to 35 LM iterations from EPnP starts)
+                    ach = BYTES_PER_SOLVE * B_PER_GPU / (split['lm_launch_ms'] * 1e-3) / 1e9
+                    line['roofline']['dominant_kernel'] = {'kernel': lm_name, 'avg_launch_ms': split['lm_launch_ms'], 'achieved': ach, 'unit': 'GB/s', 'frac': ach / HBM_PEAK_GBS,
+                                                           'algorithmic_bytes_per_launch': BYTES_PER_SOLVE * B_PER_GPU,
+                                                           'measured_on': "HIP events on the launch stream around ISOLATED launches of the LM kernel (one call at a time; the launch also carries the initialiser's re-fit as its prologue), every batch, in this run"}
+            if isinstance(extra.get('epnp_initialiser'), dict) and 'value' in extra['epnp_initialiser']:
+                ep = extra['epnp_initialiser']
+                line['reference_flow'] = {
+                    'what': "the reference's own flow on the GPU — cv2.solvePnPRansac(EPNP, 30 iterations) restated, then the LM + covariance: PnPUncert(initialiser='epnp'); "
+                            "`value` above is the one-launch K0 path, which is NOT the reference's initialiser (INTEGRATION.md section 2)",
+                    'value': ep['value'], 'unit': 'solves/s', 'ms_per_step': ep['ms_per_step'], 'issue': ep.get('issue'),
+                    'synchronous_call': ep.get('synchronous_call'), 'in_flight': ep.get('in_flight'), 'roofline': ep.get('roofline'),
+                    'launch_split_batch0_ms': {'initialiser': ep.get('epnp_ransac_launches_ms_batch0'), 'lm': ep.get('lm_launch_ms_batch0')}}
+            line['roofline']['in_flight'] = {
+                'launches_in_flight': L, 'achieved': line['value'] / world * BYTES_PER_SOLVE / 1e9, 'unit': 'GB/s',
+                'frac': line['value'] / world * BYTES_PER_SOLVE / 1e9 / HBM_PEAK_GBS,
+                'note': 'chip-level rate of the timed region: algorithmic bytes of ALL launches / wall time (launches overlap, so this is not a '
+                        'per-launch duration); `achieved` / `frac` above are per launch, from HIP events around isolated launches on one stream'}
         if comm is not None:
-            comm['gathered_rows_verified'] = gather_ok
+            if args.full:
+                comm['gathered_rows_verified'] = gather_ok
             line['comm'] = comm
         if dumped is not None:
             line['outputs_dumped'] = dumped
-        if ref_flow and world == 1 and not args.no_secondary and not stress:
+        if args.full and ref_flow and world == 1 and not args.no_secondary and not stress:
             # the explicit fast mode, measured by the same script in a child process (the parent is idle meanwhile): rounds 1-4's `value`
             import subprocess
             import tempfile
             fd, kfile = tempfile.mkstemp(prefix='mr_bench_k0_', suffix='.json')
             os.close(fd)
             cmd = [sys.executable, os.path.abspath(__file__), '--flow', 'k0', '--steps', str(args.steps), '--warmup', str(args.warmup), '--batches', str(args.batches),
-                   '--in-flight', str(args.in_flight), '--no-cpu-baseline', '--details', kfile]
+                   '--in-flight', str(args.in_flight), '--full', '--no-cpu-baseline', '--details', kfile]
             try:
                 torch.cuda.synchronize()
                 cp = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=dict(os.environ, MR_BENCH_SKIP_EPNP_SECONDARY='1'))
@@ -889,7 +902,7 @@ def run(args):
                     kj = json.loads(f.read())
                 line['k0_fast_mode'] = {
                     'what': "PnPUncert(initialiser='k0'): this repository's one-launch consensus initialiser fused with the LM — NOT the reference's initialiser "
-                            '(inlier sets differ from the reference flow\'s on ~13 % of config-2 objects); `python bench.py --flow k0 --details FILE` writes this record on its own',
+                            '(inlier sets differ from the reference flow\'s on ~13 % of config-2 objects); `python bench.py --full --flow k0 --details FILE` writes this record on its own',
                     'value': kj['value'], 'unit': 'solves/s', 'ms_per_step': kj['ms_per_step'], 'steps': kj['steps'], 'steady_state': kj.get('steady_state'),
                     'single_stream': kj.get('single_stream'), 'roofline': kj.get('roofline'), 'config': {k: kj['config'].get(k) for k in ('stages', 'launches_in_flight', 'waves_per_object', 'prewarm')},
                     'secondary_throughput': kj.get('secondary_throughput')}
@@ -897,7 +910,7 @@ def run(args):
                 line['k0_fast_mode'] = {'error': repr(e)}
             finally:
                 os.remove(kfile)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(np_batch0, perturbed_gt_init(batch0, SEED) if not stress else None, args.cpu_seconds, ref_flow,
                               'config-2 batch 0' if not stress else 'the stress batch (56x56 correspondences; float32 values, the GPU reads them rounded to fp16)')
             line.update(cb)

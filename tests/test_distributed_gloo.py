@@ -281,7 +281,7 @@ def test_bench_self_launches_its_ranks(tmp_path):
                            capture_output=True, text=True, timeout=300, env=env)
         assert r.returncode != 0 and 'needs 2 visible MI355X devices' in r.stderr
         env['MR_BENCH_OVERSUBSCRIBE'] = '1'
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2', '--batches', '2',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '6', '--warmup', '2', '--batches', '2',
                         '--no-cpu-baseline', '--no-secondary', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-1000:], r.stderr[-3000:])
@@ -361,7 +361,7 @@ def test_bench_rccl_path_with_launch_sets_and_its_fallback(tmp_path):
     communicator cannot be built (MR_RCCL_LIBRARY points nowhere: VERDICT r4 item 7b) the job falls back to torch.distributed's
     all-gather, says so in comm.backend, and still verifies the gathered rows."""
     import json, subprocess
-    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '14', '--warmup', '4', '--batches', '3', '--no-cpu-baseline', '--no-secondary']
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--steps', '14', '--warmup', '4', '--batches', '3', '--no-cpu-baseline', '--no-secondary']
     for broken in (False, True):
         env = dict(os.environ, MR_BENCH_FORCE_DIST='1', MASTER_PORT=str(29600 + int(broken)))
         if broken:

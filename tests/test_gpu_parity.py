@@ -609,7 +609,7 @@ def test_bench_line_describes_the_regime_it_measured(tmp_path, dev):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     details = tmp_path / 'bench_details.json'
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '8', '--warmup', '2', '--batches', '4', '--no-cpu-baseline',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '8', '--warmup', '2', '--batches', '4', '--no-cpu-baseline',
                         '--details', str(details), '--dump-outputs', str(tmp_path / 'out')], capture_output=True, text=True, timeout=1500)
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-500:], r.stderr[-2000:])
@@ -647,10 +647,14 @@ def test_bench_line_describes_the_regime_it_measured(tmp_path, dev):
     assert k0['value'] > d['value'] and k0['steady_state']['value'] > 0 and k0['single_stream']['value'] > 0
     assert k0['roofline']['kernel'].startswith('pnp_uncert_kernel<float, ') and k0['roofline']['kernel'].endswith('false>')
     assert 'head_to_pose_1024' in k0['secondary_throughput'] and 'epnp_initialiser' not in k0['secondary_throughput']
-    od = h['outputs_dumped']                                   # --dump-outputs: the last timed step's outputs = an isolated launch of its batch
+    _check_bench_dump(h['outputs_dumped'], tmp_path / 'out', 7, dev)
+
+
+def _check_bench_dump(od, out, step, dev):
+    """--dump-outputs: the last timed step's outputs = an isolated launch of its batch."""
     from monorun_amd import PnPEpnpLaunch
-    got = {f[:-4]: np.load(tmp_path / 'out' / f) for f in od['files']}
-    assert od['step'] == 7 and sorted(got) == ['cov', 'inlier_mask', 'pose', 'tr', 'valid'] and all(a.dtype == np.float32 for a in got.values())
+    got = {f[:-4]: np.load(out / f) for f in od['files']}
+    assert od['step'] == step and sorted(got) == ['cov', 'inlier_mask', 'pose', 'tr', 'valid'] and all(a.dtype == np.float32 for a in got.values())
     assert sum(a.nbytes for a in got.values()) <= 64e6 and got['inlier_mask'].shape == (1024, 784)
     x = [_dv(a, dev) for a in syn.pnp_boundary(syn.make_batch(B=1024, hw=28, seed=od['batch_seed']), planar=True)]
     ref = PnPEpnpLaunch(*x[:6], z_min=0.5, epnp_istd_thres=0.6, epnp_ransac_thres=x[6], inlier_opt_only=True, flags=od['flags'])
@@ -658,3 +662,31 @@ def test_bench_line_describes_the_regime_it_measured(tmp_path, dev):
     torch.cuda.synchronize()
     for k in ('valid', 'pose', 'cov', 'tr', 'mask'):
         assert np.array_equal(got['inlier_mask' if k == 'mask' else k], getattr(ref, k).cpu().numpy().astype(np.float32), equal_nan=True), k
+
+
+def test_plain_bench_run_times_the_headline_only(tmp_path, dev):
+    """bench.py without --full: the timed window, the dump and the headline line.  Nothing is measured or checked after the window
+    (no variants, roofline, output re-check, secondary figures, --flow k0 child run or CPU baselines); the line's headline fields
+    mean what they mean with --full, and the dump still equals an isolated launch of its batch."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    details = tmp_path / 'bench_details.json'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '8', '--warmup', '2', '--batches', '4',
+                        '--details', str(details), '--dump-outputs', str(tmp_path / 'out')], capture_output=True, text=True, timeout=600)
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert r.returncode == 0 and len(lines) == 1, (r.stdout[-500:], r.stderr[-2000:])
+    h = json.loads(lines[0])
+    d = json.loads(details.read_text())
+    assert h['metric'].startswith('PnP solves/sec') and h['unit'] == 'solves/s' and h['higher_is_better'] is True and h['dtype'] == 'f64'
+    assert h['flow'] == 'reference' and h['n_gpus'] == 1 and h['steps'] == 8 and h['warmup'] == 2 and h['value'] > 0
+    assert abs(h['ms_per_step'] - 1e3 * 1024 / h['value']) <= 1e-9 * h['ms_per_step']
+    assert h['valid_fraction'] > 0.95 and h['value_cold'] > 0
+    assert all(h[k] == d[k] for k in ('value', 'ms_per_step', 'value_cold', 'valid_fraction'))
+    for k in ('outputs_verified', 'value_rotation_normalised', 'value_steady_state', 'value_single_stream', 'value_k0_fast_mode', 'value_cpu_baseline',
+              'speedup_vs_cpu_1thread', 'speedup_vs_cpu_all_cores', 'comm'):
+        assert k not in h, k
+    for k in ('roofline', 'rotation_normalised', 'single_stream', 'steady_state', 'reference_flow', 'k0_fast_mode', 'cpu_baseline', 'secondary_throughput'):
+        assert k not in d, k
+    pw = d['config']['prewarm']                                # what comes before the timed window is unchanged
+    assert pw['launches'] > 0 and pw['window_before']['steps'] == 8
+    _check_bench_dump(h['outputs_dumped'], tmp_path / 'out', 7, dev)

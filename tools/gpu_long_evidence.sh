@@ -13,7 +13,7 @@ has fuzz_epnp && { TRIALS=${TRIALS:-2000} python tests/sweeps/gpu_epnp_fuzz.py >
 has repeats || exit 0
 : > $O/${T}_bench_repeats.txt
 for i in $(seq 1 ${REPEATS:-12}); do
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --details $O/.bench_details.json > /dev/null 2>&1 && python -c "
+    python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --details $O/.bench_details.json > /dev/null 2>&1 && python -c "
 import json, sys
 b = json.load(open('$O/.bench_details.json'))
 print('run %2d value %.3f M solves/s  ms_per_step %.4f  single_stream %.3f M  rotation_normalised %.3f M  kernel avg %.1f us' % ($i, b['value'] / 1e6, b['ms_per_step'], b['single_stream']['value'] / 1e6, b['value_rotation_normalised'] / 1e6, b['roofline']['isolated_launch']['kernel_ms_avg'] * 1e3))" >> $O/${T}_bench_repeats.txt

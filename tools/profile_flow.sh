@@ -20,11 +20,11 @@ done
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY --kernel-trace --output-format csv -d $OUT/pmc_sq -o p -- env REPS=6 python $R/tools/gpu_epnp_path.py > $OUT/pmc_sq.log 2>&1
 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc_lds -o p -- env REPS=6 python $R/tools/gpu_epnp_path.py > $OUT/pmc_lds.log 2>&1
 python $R/tools/summarize_flow.py $TAG > $OUT/summarize_on_box.log 2>&1        # profiles/<tag>_epnp_traffic*.json, _epnp_valu_per_launch.json exist from here on
-python $R/bench.py --steps 20 --warmup 5 --details $OUT/bench.json > $OUT/bench_line.json 2> $OUT/bench.err
-python $R/bench.py --steps 240 --warmup 24 --no-cpu-baseline --no-secondary --details $OUT/bench_240.json >> $OUT/bench_line.json 2>> $OUT/bench.err
-python $R/bench.py --workload stress --details $OUT/bench_stress.json >> $OUT/bench_line.json 2>> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bench -o t -- python $R/bench.py --steps 96 --warmup 12 --no-cpu-baseline --no-secondary > $OUT/trace_bench.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_k0 -o t -- python $R/bench.py --flow k0 --steps 96 --warmup 12 --no-cpu-baseline --no-secondary > $OUT/trace_k0.log 2>&1
+python $R/bench.py --full --steps 20 --warmup 5 --details $OUT/bench.json > $OUT/bench_line.json 2> $OUT/bench.err
+python $R/bench.py --full --steps 240 --warmup 24 --no-cpu-baseline --no-secondary --details $OUT/bench_240.json >> $OUT/bench_line.json 2>> $OUT/bench.err
+python $R/bench.py --full --workload stress --details $OUT/bench_stress.json >> $OUT/bench_line.json 2>> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_bench -o t -- python $R/bench.py --full --steps 96 --warmup 12 --no-cpu-baseline --no-secondary > $OUT/trace_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_k0 -o t -- python $R/bench.py --full --flow k0 --steps 96 --warmup 12 --no-cpu-baseline --no-secondary > $OUT/trace_k0.log 2>&1
 rocminfo | grep -E "Marketing Name|Compute Unit|Max Clock" | head -8 > $OUT/rocminfo.txt
 lscpu | grep -E "Model name|^CPU\(s\)|Thread|Core|Socket" > $OUT/lscpu.txt; nproc >> $OUT/lscpu.txt
 find $OUT -name "*.csv" | wc -l

@@ -6,7 +6,7 @@
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 STEPS=${1:-240}; WARMUP=${2:-24}
 for n in 1 2 4 8; do
-    out=$(python $ROOT/bench.py --gpus $n --steps $STEPS --warmup $WARMUP --no-cpu-baseline --no-secondary) || out="{\"n_gpus\": $n, \"error\": \"bench.py exited with $?\"}"
+    out=$(python $ROOT/bench.py --full --gpus $n --steps $STEPS --warmup $WARMUP --no-cpu-baseline --no-secondary) || out="{\"n_gpus\": $n, \"error\": \"bench.py exited with $?\"}"
     echo "$out"
     echo "$out" | python -c "
 import json, sys
