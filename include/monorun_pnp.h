@@ -294,6 +294,25 @@ int mr_pnp_exact_hessian_batched(
     uint8_t *valid, float *hess, float *cov, void *stream);
 
 /*
+ * Backward of the 4-DoF op (`pnp_uncert(..., differentiable=True)`): gradients of a loss L(pose, cov) with respect to the
+ * correspondences by the implicit function theorem at the refined pose.  One launch, one workgroup per object,
+ * deterministic (no atomics).  Inputs / strides / dtype / cameras / ranges as for mr_pnp_uncert_batched; pose (B,4) f32 and valid (B) u8
+ * as that call returned them, inlier_mask (B,P) u8 or NULL (all points); lm_all_points: 1 when the LM refined every point
+ * (inlier_opt_only=False), 0 when it refined the inliers only.  grad_pose (B,4) f32 = dL/d[yaw,tx,ty,tz] or NULL (zero);
+ * cov (B,16) f32 = the returned pose covariance and grad_cov (B,16) f32 = dL/dcov, both or neither (NULL: no covariance term).
+ * Outputs (f32, contiguous, each may be NULL): grad_x2d (B,P,2), grad_istd (B,P,2), grad_x3d (B,P,3); every entry is written (zero
+ * for masked rows and points, objects with valid = 0 and objects whose Hessian is singular or non-finite).  status (B) u8 or NULL:
+ * 0 gradients written, 1 object not valid, 2 Hessian singular or non-finite.
+ */
+int mr_pnp_uncert_backward_batched(
+    const void *x2d, const int64_t *x2d_strides, const void *istd, const int64_t *istd_strides,
+    const void *x3d, const int64_t *x3d_strides, int in_dtype,
+    const float *cam_mats, int cam_batch, const float *u_range, const float *v_range, int range_batch,
+    const float *pose, const uint8_t *inlier_mask, const uint8_t *valid, int lm_all_points,
+    const float *grad_pose, const float *cov, const float *grad_cov, int B, int P, float z_min,
+    float *grad_x2d, float *grad_istd, float *grad_x3d, uint8_t *status, void *stream);
+
+/*
  * The reference's own per-object C entry point, same signature and semantics (ext.h:1-13,
  * pnp_uncert_cpu.cpp:245-292): HOST fp64 buffers in, host results out; runs the same LM kernel on the
  * GPU for one object (blocking).  result_cov may be NULL; on failure result_cov is left untouched.

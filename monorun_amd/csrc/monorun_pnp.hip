@@ -593,6 +593,7 @@ struct PnpCallTable {
 #include "pnp_kernel.inc"
 #include "pnp6_kernel.inc"
 #include "hessian_kernel.inc"
+#include "pnp_backward_kernel.inc"
 #include "pnp_noc_kernel.inc"
 #include "epnp_kernel.inc"
 #include "epnp_eig_low4.inc"
@@ -1534,6 +1535,40 @@ int mr_pnp_exact_hessian_batched(
         case MR_F32: hipLaunchKernelGGL((exact_hessian_kernel<float>), dim3(B), dim3(256), 0, st, a); break;
         case MR_F16: hipLaunchKernelGGL((exact_hessian_kernel<__half>), dim3(B), dim3(256), 0, st, a); break;
         case MR_F64: hipLaunchKernelGGL((exact_hessian_kernel<double>), dim3(B), dim3(256), 0, st, a); break;
+        default: return MR_ERR_UNSUPPORTED;
+    }
+    HIP_TRY(hipGetLastError());
+    return MR_OK;
+}
+
+int mr_pnp_uncert_backward_batched(
+    const void *x2d, const int64_t *x2d_strides, const void *istd, const int64_t *istd_strides,
+    const void *x3d, const int64_t *x3d_strides, int in_dtype,
+    const float *cam_mats, int cam_batch, const float *u_range, const float *v_range, int range_batch,
+    const float *pose, const uint8_t *inlier_mask, const uint8_t *valid, int lm_all_points,
+    const float *grad_pose, const float *cov, const float *grad_cov, int B, int P, float z_min,
+    float *grad_x2d, float *grad_istd, float *grad_x3d, uint8_t *status, void *stream) {
+    if (B < 0 || P < 1) return MR_ERR_BAD_ARGUMENT;
+    if (B == 0) return MR_OK;
+    if (!x2d || !istd || !x3d || !x2d_strides || !istd_strides || !x3d_strides || !cam_mats || !u_range || !v_range || !pose || !valid)
+        return MR_ERR_BAD_ARGUMENT;
+    if ((cov == nullptr) != (grad_cov == nullptr)) return MR_ERR_BAD_ARGUMENT;
+    if ((cam_batch != 1 && cam_batch != B) || (range_batch != 1 && range_batch != B)) return MR_ERR_BAD_ARGUMENT;
+    PnpBwdArgs a;
+    memset(&a, 0, sizeof a);
+    a.x2d = x2d; a.istd = istd; a.x3d = x3d;
+    for (int i = 0; i < 3; ++i) { a.s2[i] = x2d_strides[i]; a.sw[i] = istd_strides[i]; a.s3[i] = x3d_strides[i]; }
+    a.K = cam_mats; a.K_stride = (cam_batch == 1) ? 0 : 9;
+    a.ur = u_range; a.vr = v_range; a.r_stride = (range_batch == 1) ? 0 : 2;
+    a.pose = pose; a.mask = inlier_mask; a.valid = valid; a.lm_all = lm_all_points ? 1 : 0;
+    a.grad_pose = grad_pose; a.cov = cov; a.grad_cov = grad_cov;
+    a.B = B; a.P = P; a.z_min = (double)z_min;
+    a.g2 = grad_x2d; a.gw = grad_istd; a.g3 = grad_x3d; a.status = status;
+    hipStream_t st = (hipStream_t)stream;
+    switch (in_dtype) {
+        case MR_F32: hipLaunchKernelGGL((pnp_uncert_backward_kernel<float>), dim3(B), dim3(256), 0, st, a); break;
+        case MR_F16: hipLaunchKernelGGL((pnp_uncert_backward_kernel<__half>), dim3(B), dim3(256), 0, st, a); break;
+        case MR_F64: hipLaunchKernelGGL((pnp_uncert_backward_kernel<double>), dim3(B), dim3(256), 0, st, a); break;
         default: return MR_ERR_UNSUPPORTED;
     }
     HIP_TRY(hipGetLastError());

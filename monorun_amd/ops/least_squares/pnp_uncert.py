@@ -601,9 +601,135 @@ def exact_hessian_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range
     return valid, cov, hess
 
 
+def pnp_uncert_backward_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, pose4, inlier_mask_u8, valid_u8, grad_pose,
+                               cov=None, grad_cov=None, z_min=0.5, lm_all_points=False, needs=(True, True, True), with_status=False):
+    """Backward of the 4-DoF op (``mr_pnp_uncert_backward_batched``): gradients of a loss L(pose, cov) with respect to
+    the correspondences at the pose4 (B,4) f32 / inlier_mask_u8 (B,P) u8 | None / valid_u8 (B,) u8 the forward returned.
+    grad_pose (B,4) = dL/d[yaw, t] or None (zero); cov (B,4,4) = the returned covariance and grad_cov (B,4,4) = dL/dcov, both or None.
+    lm_all_points: the LM refined every point (inlier_opt_only=False).  needs: which of (x2d, istd, x3d) to compute.
+    Returns (grad_x2d f32 (B,P,2) | None, grad_istd f32 (B,P,2) | None, grad_x3d f32 (B,P,3) | None, status u8 (B,) | None)."""
+    lib = _lib.load()
+    dev = coords_2d.device
+    if dev.type != 'cuda':
+        raise RuntimeError('monorun_amd PnP backward runs on an MI355X only (no CPU fallback)')
+    if (cov is None) != (grad_cov is None):
+        raise ValueError('cov and grad_cov go together')
+    B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
+    dt = coords_2d.dtype if coords_2d.dtype in _DTYPES else torch.float32
+    prep = lambda t: t.detach() if (t.dtype == dt and t.device == dev) else t.detach().to(device=dev, dtype=dt)
+    x2d, istd, x3d = prep(coords_2d), prep(coords_2d_istd), prep(coords_3d)
+    assert x2d.shape == (B, P, 2) and istd.shape == (B, P, 2) and x3d.shape == (B, P, 3)
+    f32 = dict(device=dev, dtype=torch.float32)
+    cam = cam_mats.detach().to(**f32).reshape(-1, 3, 3).contiguous()
+    ur = u_range.detach().to(**f32).reshape(-1, 2).contiguous()
+    vr = v_range.detach().to(**f32).reshape(-1, 2).contiguous()
+    pose = pose4.detach().to(**f32).reshape(B, 4).contiguous()
+    mask = inlier_mask_u8.detach().to(device=dev, dtype=torch.uint8).contiguous() if inlier_mask_u8 is not None else None
+    valid = valid_u8.detach().to(device=dev, dtype=torch.uint8).contiguous()
+    gp = grad_pose.detach().to(**f32).reshape(B, 4).contiguous() if grad_pose is not None else None
+    c = cov.detach().to(**f32).reshape(B, 16).contiguous() if cov is not None else None
+    gc = grad_cov.detach().to(**f32).reshape(B, 16).contiguous() if grad_cov is not None else None
+    g2 = torch.empty(B, P, 2, **f32) if needs[0] else None
+    gw = torch.empty(B, P, 2, **f32) if needs[1] else None
+    g3 = torch.empty(B, P, 3, **f32) if needs[2] else None
+    status = torch.empty(B, device=dev, dtype=torch.uint8) if with_status else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    if B > 0:
+        with torch.cuda.device(dev):
+            _lib.check(lib.mr_pnp_uncert_backward_batched(
+                x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d), _DTYPES[dt],
+                cam.data_ptr(), cam.shape[0], ur.data_ptr(), vr.data_ptr(), ur.shape[0],
+                pose.data_ptr(), ptr(mask), valid.data_ptr(), int(bool(lm_all_points)), ptr(gp), ptr(c), ptr(gc), B, P, float(z_min),
+                ptr(g2), ptr(gw), ptr(g3), ptr(status), torch.cuda.current_stream(dev).cuda_stream))
+    return g2, gw, g3, status
+
+
+def _pnp_uncert_forward(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min, epnp_istd_thres, epnp_ransac_thres,
+                        inlier_opt_only, forward_exact_hessian, use_6dof, initialiser, cov_symeig_rule, epnp_first_round):
+    """The forward launches of ``pnp_uncert``.  Returns (outputs, saved): the op's tuple, and for the 4-DoF path the device tensors the
+    backward needs (x2d, istd, x3d as the kernels read them, pose f32 (B,4), mask u8 (B,P), valid u8 (B,), cov f32 (B,4,4)); None for 6-DoF."""
+    with torch.no_grad():
+        src_dev = coords_2d.device
+        if src_dev.type != 'cuda':
+            if not torch.cuda.is_available():
+                raise RuntimeError('monorun_amd.ops.pnp_uncert needs an MI355X (HIP) device; no CPU fallback exists')
+            dev = torch.device('cuda', torch.cuda.current_device())
+            mv = lambda t: t.to(dev) if t is not None else None
+            coords_2d, coords_2d_istd, coords_3d = mv(coords_2d), mv(coords_2d_istd), mv(coords_3d)
+        if initialiser is None:
+            initialiser = DEFAULT_INITIALISER
+        if initialiser == 'epnp':
+            valid, pose, cov, _, mask = pnp_uncert_epnp_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min=z_min,
+                                                               epnp_istd_thres=epnp_istd_thres, epnp_ransac_thres=epnp_ransac_thres,
+                                                               inlier_opt_only=inlier_opt_only, first_round=epnp_first_round)[:5]
+        elif initialiser == 'k0':
+            valid, pose, cov, _, mask, _ = pnp_uncert_device(
+                coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min=z_min,
+                epnp_istd_thres=epnp_istd_thres, epnp_ransac_thres=epnp_ransac_thres, inlier_opt_only=inlier_opt_only)
+        else:
+            raise ValueError(f"initialiser must be 'k0' or 'epnp', got {initialiser!r}")
+        odt = coords_2d.dtype
+        if use_6dof and cov_symeig_rule:
+            raise ValueError('cov_symeig_rule tests the 4x4 covariance of [yaw, t] (pnp_uncert.py:77-85); it has no meaning for the 6x6 '
+                             'covariance that use_6dof=True returns')
+        if use_6dof:
+            valid6, pose6, cov6, _ = pnp6_refine_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, mask, pose, valid, z_min=z_min)
+            return ((valid & valid6).to(device=src_dev, dtype=torch.bool), pose6[:, :3].to(device=src_dev, dtype=odt),
+                    pose6[:, 3:].to(device=src_dev, dtype=odt), cov6.to(device=src_dev, dtype=odt), mask.to(device=src_dev, dtype=torch.bool)), None
+        if forward_exact_hessian:
+            valid, cov, _ = exact_hessian_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, pose, mask, valid, z_min=z_min)
+        if cov_symeig_rule:
+            cov = cov.contiguous()
+            cov_symeig_rule_device(valid, cov)
+        ret_val = valid.to(device=src_dev, dtype=torch.bool)
+        r_vec = pose[:, :1].to(device=src_dev, dtype=odt)
+        t_vec = pose[:, 1:].to(device=src_dev, dtype=odt)
+        pose_cov = cov.to(device=src_dev, dtype=odt)
+        inlier_mask = mask.to(device=src_dev, dtype=torch.bool)
+    return (ret_val, r_vec, t_vec, pose_cov, inlier_mask), (coords_2d, coords_2d_istd, coords_3d, pose, mask, valid, cov)
+
+
+class _PnPUncertFunction(torch.autograd.Function):
+    """``pnp_uncert(..., differentiable=True)``: the forward launches of the op unchanged; the backward is one launch of
+    ``mr_pnp_uncert_backward_batched`` (implicit differentiation at the refined pose).  Differentiable in the three
+    coordinate tensors; cam_mats, u_range, v_range and epnp_ransac_thres get None (as the reference's get_jacobians)."""
+
+    @staticmethod
+    def forward(ctx, coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, epnp_ransac_thres, kw):
+        (ret_val, r_vec, t_vec, pose_cov, inlier_mask), saved = _pnp_uncert_forward(
+            coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, epnp_ransac_thres=epnp_ransac_thres, **kw)
+        ctx.save_for_backward(*saved)
+        ctx.cam, ctx.ur, ctx.vr = cam_mats.detach(), u_range.detach(), v_range.detach()
+        ctx.z_min, ctx.lm_all = kw['z_min'], not kw['inlier_opt_only']
+        ctx.src = [(t.device, t.dtype) for t in (coords_2d, coords_2d_istd, coords_3d)]
+        ctx.mark_non_differentiable(ret_val, inlier_mask)
+        # r_vec / t_vec may be views of one pose buffer: hand out tensors of their own (same values)
+        return ret_val, r_vec.clone(), t_vec.clone(), pose_cov, inlier_mask
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _g_ret, g_r, g_t, g_cov, _g_mask):
+        x2d, istd, x3d, pose, mask, valid, cov = ctx.saved_tensors
+        needs = tuple(ctx.needs_input_grad[:3])
+        if not any(needs) or (g_r is None and g_t is None and g_cov is None):
+            return (None,) * 8
+        B, dev = pose.shape[0], pose.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        gp = torch.zeros(B, 4, **f32)
+        if g_r is not None:
+            gp[:, :1] = g_r.to(**f32)
+        if g_t is not None:
+            gp[:, 1:] = g_t.to(**f32)
+        gc = g_cov.to(**f32) if g_cov is not None else None
+        grads = pnp_uncert_backward_device(x2d, istd, x3d, ctx.cam, ctx.ur, ctx.vr, pose, mask, valid, gp, cov if gc is not None else None, gc,
+                                           z_min=ctx.z_min, lm_all_points=ctx.lm_all, needs=needs)[:3]
+        out = [g.to(device=d, dtype=t) if g is not None else None for g, (d, t) in zip(grads, ctx.src)]
+        return tuple(out) + (None,) * 5
+
+
 def pnp_uncert(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min=0.5, epnp_istd_thres=1.0,
                epnp_ransac_thres=None, inlier_opt_only=False, forward_exact_hessian=False, use_6dof=False, initialiser=None, cov_symeig_rule=False,
-               epnp_first_round=None):
+               epnp_first_round=None, differentiable=False):
     """Functional form of the op on torch tensors (argument names and defaults: pnp_uncert.py:7-11 of the reference).
 
     coords_2d / coords_2d_istd (B,P,2), coords_3d (B,P,3), cam_mats (B|1,3,3), u_range / v_range (B|1,2),
@@ -633,59 +759,33 @@ def pnp_uncert(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range,
     angle-axis vector, pose_cov the (B,6,6) covariance of [rx, ry, rz, tx, ty, tz] (solver Jacobian); ret_val additionally
     requires the 6-DoF solve to be usable.  Because the flag is dead in the reference, every shipped config keeps running
     the 4-DoF path.
+    differentiable (not a reference keyword; default False): when True and a coordinate tensor requires grad, the op is a
+    ``torch.autograd.Function`` — the same launches and bit-identical outputs, and r_vec / t_vec / pose_cov carry gradients to
+    coords_2d, coords_2d_istd and coords_3d (the reference's documented backward, pnp_uncert.py:102-105, with the exact Hessian;
+    DESIGN.md §10).  Not with use_6dof=True or forward_exact_hessian=True (ValueError).
     """
-    with torch.no_grad():
-        src_dev = coords_2d.device
-        if src_dev.type != 'cuda':
-            if not torch.cuda.is_available():
-                raise RuntimeError('monorun_amd.ops.pnp_uncert needs an MI355X (HIP) device; no CPU fallback exists')
-            dev = torch.device('cuda', torch.cuda.current_device())
-            mv = lambda t: t.to(dev) if t is not None else None
-            coords_2d, coords_2d_istd, coords_3d = mv(coords_2d), mv(coords_2d_istd), mv(coords_3d)
-        if initialiser is None:
-            initialiser = DEFAULT_INITIALISER
-        if initialiser == 'epnp':
-            valid, pose, cov, _, mask = pnp_uncert_epnp_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min=z_min,
-                                                               epnp_istd_thres=epnp_istd_thres, epnp_ransac_thres=epnp_ransac_thres,
-                                                               inlier_opt_only=inlier_opt_only, first_round=epnp_first_round)[:5]
-        elif initialiser == 'k0':
-            valid, pose, cov, _, mask, _ = pnp_uncert_device(
-                coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min=z_min,
-                epnp_istd_thres=epnp_istd_thres, epnp_ransac_thres=epnp_ransac_thres, inlier_opt_only=inlier_opt_only)
-        else:
-            raise ValueError(f"initialiser must be 'k0' or 'epnp', got {initialiser!r}")
-        odt = coords_2d.dtype
-        if use_6dof and cov_symeig_rule:
-            raise ValueError('cov_symeig_rule tests the 4x4 covariance of [yaw, t] (pnp_uncert.py:77-85); it has no meaning for the 6x6 '
-                             'covariance that use_6dof=True returns')
-        if use_6dof:
-            valid6, pose6, cov6, _ = pnp6_refine_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, mask, pose, valid, z_min=z_min)
-            return ((valid & valid6).to(device=src_dev, dtype=torch.bool), pose6[:, :3].to(device=src_dev, dtype=odt),
-                    pose6[:, 3:].to(device=src_dev, dtype=odt), cov6.to(device=src_dev, dtype=odt), mask.to(device=src_dev, dtype=torch.bool))
-        if forward_exact_hessian:
-            valid, cov, _ = exact_hessian_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, pose, mask, valid, z_min=z_min)
-        if cov_symeig_rule:
-            cov = cov.contiguous()
-            cov_symeig_rule_device(valid, cov)
-        ret_val = valid.to(device=src_dev, dtype=torch.bool)
-        r_vec = pose[:, :1].to(device=src_dev, dtype=odt)
-        t_vec = pose[:, 1:].to(device=src_dev, dtype=odt)
-        pose_cov = cov.to(device=src_dev, dtype=odt)
-        inlier_mask = mask.to(device=src_dev, dtype=torch.bool)
-    return ret_val, r_vec, t_vec, pose_cov, inlier_mask
+    if differentiable and (use_6dof or forward_exact_hessian):
+        raise ValueError('differentiable=True covers the 4-DoF pose with the J^T J covariance: not use_6dof=True or forward_exact_hessian=True')
+    kw = dict(z_min=z_min, epnp_istd_thres=epnp_istd_thres, inlier_opt_only=inlier_opt_only, forward_exact_hessian=forward_exact_hessian,
+              use_6dof=use_6dof, initialiser=initialiser, cov_symeig_rule=cov_symeig_rule, epnp_first_round=epnp_first_round)
+    if differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in (coords_2d, coords_2d_istd, coords_3d)):
+        return _PnPUncertFunction.apply(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, epnp_ransac_thres, kw)
+    return _pnp_uncert_forward(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, epnp_ransac_thres=epnp_ransac_thres, **kw)[0]
 
 
 @PNP.register_module()
 class PnPUncert(torch.nn.Module):
 
     def __init__(self, z_min=0.5, epnp_istd_thres=0.6, inlier_opt_only=True, coord_istd_normalize=False,
-                 forward_exact_hessian=False, use_6dof=False, eps=1e-6, initialiser=None, epnp_first_round=None, cov_symeig_rule=False):
+                 forward_exact_hessian=False, use_6dof=False, eps=1e-6, initialiser=None, epnp_first_round=None, cov_symeig_rule=False,
+                 differentiable=False):
         """Module form (constructor keywords of the reference, pnp_uncert.py:93-99; no parameters, no buffers).
         epnp_istd_thres: a point is an istd inlier when both of its istd components reach this factor times the object's
         mean; inlier_opt_only: the LM refines on the inlier set only; coord_istd_normalize: divide the istd map by its
         per-object mean (clamped at eps) first.  initialiser ('k0' | 'epnp'), epnp_first_round, cov_symeig_rule (not reference
         keywords): see ``pnp_uncert``.  The reference's own config dict builds the REFERENCE's flow (initialiser='epnp', the default since
-        round 5); ``initialiser='k0'`` selects the one-launch fast mode."""
+        round 5); ``initialiser='k0'`` selects the one-launch fast mode.  differentiable (not a reference keyword):
+        gradients flow from yaw / t_vec / pose_cov to the coordinate maps (``pnp_uncert``; the istd normalisation stays in torch)."""
         super().__init__()
         if initialiser is None:
             initialiser = DEFAULT_INITIALISER
@@ -693,6 +793,9 @@ class PnPUncert(torch.nn.Module):
             raise ValueError(f"initialiser must be 'k0' or 'epnp', got {initialiser!r}")
         if cov_symeig_rule and use_6dof:
             raise ValueError('cov_symeig_rule applies to the 4-DoF covariance only (use_6dof=True returns a 6x6 one)')
+        if differentiable and (use_6dof or forward_exact_hessian):
+            raise ValueError('differentiable=True covers the 4-DoF pose with the J^T J covariance: not use_6dof=True or forward_exact_hessian=True')
+        self.differentiable = differentiable
         self.initialiser, self.epnp_first_round, self.cov_symeig_rule = initialiser, epnp_first_round, cov_symeig_rule
         self.z_min, self.epnp_istd_thres, self.inlier_opt_only = z_min, epnp_istd_thres, inlier_opt_only
         self.coord_istd_normalize, self.eps = coord_istd_normalize, eps
@@ -706,4 +809,4 @@ class PnPUncert(torch.nn.Module):
                           epnp_istd_thres=self.epnp_istd_thres, epnp_ransac_thres=epnp_ransac_thres,
                           inlier_opt_only=self.inlier_opt_only, forward_exact_hessian=self.forward_exact_hessian,
                           use_6dof=self.use_6dof, initialiser=self.initialiser, epnp_first_round=self.epnp_first_round,
-                          cov_symeig_rule=self.cov_symeig_rule)
+                          cov_symeig_rule=self.cov_symeig_rule, differentiable=self.differentiable)

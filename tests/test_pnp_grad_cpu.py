@@ -1,0 +1,146 @@
+"""CPU side of the differentiable ``pnp_uncert``: the fp64 reference the GPU backward is measured against
+(tests/pnp_grad_ref.py) checked against the reference repository's own point-wise Jacobians (G13) and against finite differences of a
+re-solved pose; the public keyword, its invalid combinations, and the C entry point's argument checks.  No GPU needed."""
+import inspect
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+from torch.func import jacfwd, vmap
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import pnp_grad_ref as ref  # noqa: E402
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'g13_pointwise_jacobians.npz')
+T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.float64)
+
+
+def test_reference_pointwise_jacobians_equal_g13():
+    """dr/dX, dr/distd and dr/dtheta of the fp64 reference (autodiff, masks frozen at the pose) are the reference repository's
+    get_jacobians output, and the rows it zeroes are exactly the reference's zero rows."""
+    g = np.load(GOLDEN)
+    x2d, istd, x3d, K, ur, vr = (T(g[k]) for k in ('x2d', 'istd', 'x3d', 'K', 'u_range', 'v_range'))
+    pose = torch.cat([T(g['yaw']), T(g['t'])], 1)
+    inl = torch.from_numpy(g['mask'])
+    m_lm, m_cov = ref.row_masks(x2d, x3d, K, ur, vr, float(g['z_min']), pose, inl, lm_all=False)
+    d_x3d = vmap(jacfwd(ref.resid, argnums=3))(pose, x2d, istd, x3d, K, m_cov)             # (B,P,2,P,3): point-diagonal
+    d_x3d = torch.einsum('bpkpm->bpkm', d_x3d)
+    d_istd = torch.einsum('bpkpl->bpkl', vmap(jacfwd(ref.resid, argnums=2))(pose, x2d, istd, x3d, K, m_cov)).diagonal(dim1=2, dim2=3)
+    d_pose = vmap(jacfwd(ref.resid, argnums=0))(pose, x2d, istd, x3d, K, m_cov)             # (B,P,2,4)
+    jpw, jew = T(g['jac_pw_c3d']), T(g['jac_ew_istd'])
+    zero = (jpw.abs().sum(3) == 0)
+    assert zero.any() and (~zero).any()
+    assert torch.equal(zero, m_cov == 0)                                                    # z clip, per-axis uv clip, outliers
+    torch.testing.assert_close(d_x3d, jpw, rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(d_pose[..., 1:], T(g['jac_t_vec']), rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(d_pose[..., :1], T(g['jac_yaw']), rtol=1e-12, atol=1e-12)
+    # jac_ew_istd is the clamped unweighted error, zeroed at outliers only; on the rows the cost keeps it is dr/distd.  (A clipped
+    # row has a zero pose Jacobian in the reference too, so neither J^T r nor J^T J sees its istd.)
+    keep = m_cov > 0
+    torch.testing.assert_close(d_istd[keep], jew[keep], rtol=1e-12, atol=1e-12)
+    assert torch.equal(jew[~inl], torch.zeros_like(jew[~inl]))
+
+
+def _problem(seed, B=2, P=32):
+    """Unclipped objects (no z or uv clip near the solution) with outliers: the masks stay fixed under small perturbations."""
+    rng = np.random.default_rng(seed)
+    K = np.array([[707.0912, 0.0, 601.8873], [0.0, 707.0912, 183.1104], [0.0, 0.0, 1.0]])[None].repeat(B, 0)
+    K[1, 0, 1] = 2.0
+    yaw = rng.uniform(-np.pi, np.pi, B)
+    t = np.stack([rng.uniform(-4, 4, B), rng.uniform(1, 2, B), rng.uniform(8, 25, B)], 1)
+    x3d = (rng.uniform(-0.5, 0.5, (B, P, 3)) + np.array([0.0, -0.5, 0.0])) * np.array([3.9, 1.5, 1.6])
+    pose = np.concatenate([yaw[:, None], t], 1)
+    pi, _ = vmap(ref._proj)(T(pose), T(x3d), T(K))
+    x2d = pi.numpy() + rng.normal(0, 2.0, (B, P, 2))
+    inl = rng.random((B, P)) > 0.2
+    x2d[~inl] += rng.normal(0, 30.0, ((~inl).sum(), 2))
+    istd = np.exp(-rng.normal(np.log(2.0), 0.4, (B, P, 2))) / 10.0
+    ur = np.array([[-1e4, 1e4]]).repeat(B, 0)
+    return T(x2d), T(istd), T(x3d), T(K), T(ur), T(ur.copy()), T(pose + rng.normal(0, 0.02, (B, 4))), torch.from_numpy(inl)
+
+
+def _solve(x2d, istd, x3d, K, m_lm, theta, H=None):
+    """Newton on F = J^T r = 0 (masks fixed) to fp64 round-off; with H given, the chord method with that matrix (a re-solve after a
+    perturbation of 1e-6 converges in a few steps to the same root)."""
+    for _ in range(40):
+        if H is None:
+            F, Hk = ref.stationarity(theta, x2d, istd, x3d, K, m_lm)
+        else:
+            F, Hk = vmap(ref._F)(theta, x2d, istd, x3d, K, m_lm), H
+        step = torch.linalg.solve(Hk, F)
+        theta = theta - step
+        if step.abs().max() < 1e-15:
+            break
+    return theta
+
+
+@pytest.mark.parametrize('lm_all', [False, True])
+def test_reference_gradients_match_finite_differences_of_a_resolve(lm_all):
+    """The implicit-function gradients of L = <gp, theta*(x)> + <G, C(theta*(x), x)> match central differences of a tight Newton
+    re-solve at fixed masks.  Tolerance: 2e-6 of the largest gradient of the same tensor (the step, 1e-6 of the coordinate scale,
+    leaves a truncation error ~1e-10 relative; round-off of the re-solved loss over 2h is ~1e-9)."""
+    x2d, istd, x3d, K, ur, vr, theta0, inl = _problem(5 + lm_all)
+    B = x2d.shape[0]
+    m_lm, m_cov = ref.row_masks(x2d, x3d, K, ur, vr, 0.5, theta0, inl, lm_all)
+    theta = _solve(x2d, istd, x3d, K, m_lm, theta0)
+    H = ref.stationarity(theta, x2d, istd, x3d, K, m_lm)[1]
+    rng = np.random.default_rng(11)
+    gp, G = T(rng.normal(size=(B, 4))), T(rng.normal(size=(B, 4, 4)))
+    C = torch.linalg.inv(ref.jtj(theta, x2d, istd, x3d, K, m_cov))
+    g2, gw, g3, st = ref.pnp_grad_ref(x2d, istd, x3d, K, ur, vr, 0.5, theta, inl, torch.ones(B, dtype=torch.bool), lm_all, gp, C, G)
+    assert torch.equal(st, torch.zeros(B, dtype=torch.uint8))
+
+    def loss(a, b, c):
+        th = _solve(a, b, c, K, m_lm, theta, H)
+        Cc = torch.linalg.inv(ref.jtj(th, a, b, c, K, m_cov))
+        return float((gp * th).sum() + (G * Cc).sum())
+
+    inputs = [x2d, istd, x3d]
+    for which, (g, scale) in enumerate([(g2, 1.0), (gw, 0.1), (g3, 1.0)]):
+        h = 1e-6 * scale
+        flat = g.reshape(-1)
+        idx = list(rng.choice(flat.numel(), 5, replace=False)) + [int(flat.abs().argmax())]
+        for i in idx:
+            plus = [t.clone() for t in inputs]
+            minus = [t.clone() for t in inputs]
+            plus[which].view(-1)[i] += h
+            minus[which].view(-1)[i] -= h
+            fd = (loss(*plus) - loss(*minus)) / (2 * h)
+            assert abs(fd - float(flat[i])) <= 2e-6 * float(flat.abs().max()), (which, i, fd, float(flat[i]))
+
+
+def test_differentiable_keyword_and_builder():
+    from monorun_amd.ops import build_pnp, pnp_uncert, PnPUncert
+    assert inspect.signature(pnp_uncert).parameters['differentiable'].default is False
+    assert inspect.signature(PnPUncert).parameters['differentiable'].default is False
+    assert PnPUncert(differentiable=True).differentiable is True
+    m = build_pnp(dict(type='PnPUncert', z_min=0.5, epnp_istd_thres=0.6, inlier_opt_only=True, forward_exact_hessian=False, differentiable=True))
+    assert m.differentiable is True and build_pnp(dict(type='PnPUncert')).differentiable is False
+    from monorun_amd.pose_head import UncertPropPnPOptimizer
+    assert UncertPropPnPOptimizer(pnp=dict(type='PnPUncert', differentiable=True)).pnp.differentiable is True
+
+
+def test_invalid_combinations_raise_value_error():
+    from monorun_amd.ops import pnp_uncert, PnPUncert
+    for kw in (dict(use_6dof=True), dict(forward_exact_hessian=True)):
+        with pytest.raises(ValueError):
+            PnPUncert(differentiable=True, **kw)
+        x = torch.zeros(1, 8, 2, requires_grad=True)
+        with pytest.raises(ValueError):                     # raised before any device is needed
+            pnp_uncert(x, torch.ones(1, 8, 2), torch.zeros(1, 8, 3), torch.eye(3)[None], torch.zeros(1, 2), torch.zeros(1, 2),
+                       differentiable=True, **kw)
+
+
+def test_backward_symbol_exported_and_argument_checks():
+    from monorun_amd import _lib
+    assert 'mr_pnp_uncert_backward_batched' in _lib.EXPORTED_SYMBOLS
+    lib = _lib.load()
+    f = lib.mr_pnp_uncert_backward_batched
+    nulls = lambda B: (None, None, None, None, None, None, 0, None, 1, None, None, 1, None, None, None, 0, None, None, None, B, 16, 0.5,
+                       None, None, None, None, None)
+    assert f(*nulls(4)) == -1
+    assert f(*nulls(0)) == 0
+    assert f(*nulls(-1)) == -1
+    assert lib.mr_pnp_version() == 100
