@@ -394,6 +394,26 @@ int mr_nms_bev_batched(const float *boxes_xyxyr, const float *scores, const int3
                        float thr, int64_t *keep, int32_t *num_keep, void *stream);
 
 /*
+ * N5: aligned rotated 3-D IoU of the pose head's training loss — replaces the reference's
+ * bbox3d_overlaps_aligned_torch (monorun/core/bbox_3d/iou_calculators/bbox3d_iou_calculator.py:166-192), whose BEV step is the
+ * numba-CUDA kernel rotate_iou_kernel_eval_aligned.  One thread per pair: box i against query box i, i < n.
+ *   boxes, qboxes: device f32 rows [x, y, z, l, h, w, ry], row i at boxes + i * boxes_row_stride (stride in elements, >= 7;
+ *   the 7 values of a row are contiguous).  criterion -1 IoU, 0 over the box volume, 1 over the query volume, 2 intersection
+ *   volume (each clamped to [0, 1]).  z_axis 0..2 is the height axis (1 for KITTI camera boxes), z_center the height centre
+ *   (1.0: the coordinate is the bottom of the box).
+ *   Height rules, selected by flags:
+ *     0 (the "reference" rule):  the lower edge of the overlap is min(box top, query top), as the reference's torch function
+ *                                computes it (:145, torch.min) — the value its training loss and score head use;
+ *     MR_IOU3D_GEOMETRIC_HEIGHT: max(box top, query top), the geometric overlap, as the reference's numpy function (:84).
+ *   iou (n) f32 receives the IoU; rinc (n) f32, or NULL, the BEV intersection area (devRotateIoUEval(box, qbox, 2)).
+ *   n = 0 launches nothing.  Returns MR_ERR_BAD_ARGUMENT for n < 0, a criterion outside -1..2, z_axis outside 0..2, a row stride
+ *   below 7, unknown flag bits or a NULL pointer.
+ */
+#define MR_IOU3D_GEOMETRIC_HEIGHT 0x1
+int mr_bbox3d_overlaps_aligned(const float *boxes, int64_t boxes_row_stride, const float *qboxes, int64_t qboxes_row_stride, int n,
+                               int criterion, int z_axis, float z_center, int flags, float *iou, float *rinc, void *stream);
+
+/*
  * N2: KITTI object evaluator, device side — replaces the numba / numba-CUDA code of
  * monorun/core/evaluation/kitti_utils/eval.py and rotate_iou.py.  All arrays are device pointers; images are addressed
  * through exclusive prefix offsets (n_img+1 entries).  Box rows are double[12]:

@@ -24,6 +24,7 @@ MR_EPNP_CV_EARLY_RETURN = 0x1000
 MR_WAVES_SHIFT = 8
 MR_LM_MAXIT_SHIFT = 16
 MR_EPNP_FIRST_ROUND_SHIFT = 24
+MR_IOU3D_GEOMETRIC_HEIGHT = 0x1
 
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared']
 
@@ -34,7 +35,7 @@ def _stale():
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    deps = [SRC, os.path.join(_HERE, "csrc", "pnp_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_kernel_body.inc"), os.path.join(_HERE, "csrc", "pnp6_kernel.inc"), os.path.join(_HERE, "csrc", "hessian_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_backward_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_noc_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_eig_low4.inc"), os.path.join(_HERE, "csrc", "epnp_stages.inc"), os.path.join(_HERE, "csrc", "epnp_consensus_body.inc"), os.path.join(_HERE, "csrc", "kitti_eval_kernel.inc"), os.path.join(INCLUDE, "monorun_pnp.h")]
+    deps = [SRC, os.path.join(_HERE, "csrc", "pnp_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_kernel_body.inc"), os.path.join(_HERE, "csrc", "pnp6_kernel.inc"), os.path.join(_HERE, "csrc", "hessian_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_backward_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_noc_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_eig_low4.inc"), os.path.join(_HERE, "csrc", "epnp_stages.inc"), os.path.join(_HERE, "csrc", "epnp_consensus_body.inc"), os.path.join(_HERE, "csrc", "kitti_eval_kernel.inc"), os.path.join(_HERE, "csrc", "iou3d_kernel.inc"), os.path.join(INCLUDE, "monorun_pnp.h")]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -134,6 +135,8 @@ def load():
     lib.mr_nms_bev_batched.restype = i32
     lib.mr_nms_bev_batched.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
     i64 = ctypes.c_int64
+    lib.mr_bbox3d_overlaps_aligned.restype = i32
+    lib.mr_bbox3d_overlaps_aligned.argtypes = [vp, i64, vp, i64, i32, i32, i32, f32, i32, vp, vp, vp]
     lib.mr_kitti_overlaps.restype = i32
     lib.mr_kitti_overlaps.argtypes = [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp]
     lib.mr_kitti_match_workspace_bytes.restype = i64
@@ -153,5 +156,5 @@ def check(code):
 
 
 EXPORTED_SYMBOLS = ('mr_pnp_version', 'mr_spin', 'mr_pick_waves', 'mr_pnp_error_string', 'mr_pnp_last_hip_error', 'mr_pnp_device_count',
-                    'mr_pnp_uncert_batched', 'mr_epnp_ransac_batched', 'mr_epnp_ransac_grouped', 'mr_epnp_workspace_bytes', 'mr_pnp_uncert_from_init_batched', 'mr_pnp_uncert_from_init_grouped', 'mr_pnp_uncert_from_epnp_grouped', 'mr_cov_symeig_rule', 'mr_pnp6_refine_batched', 'mr_pnp_exact_hessian_batched', 'mr_pnp_uncert_backward_batched', 'pnp_uncert', 'mr_noc_decode_batched', 'mr_pnp_from_head_batched', 'mr_nms_bev_batched', 'pnp_noc_uncert', 'pnp_noc_cov_uncert', 'mr_pnp_noc_batched',
+                    'mr_pnp_uncert_batched', 'mr_epnp_ransac_batched', 'mr_epnp_ransac_grouped', 'mr_epnp_workspace_bytes', 'mr_pnp_uncert_from_init_batched', 'mr_pnp_uncert_from_init_grouped', 'mr_pnp_uncert_from_epnp_grouped', 'mr_cov_symeig_rule', 'mr_pnp6_refine_batched', 'mr_pnp_exact_hessian_batched', 'mr_pnp_uncert_backward_batched', 'pnp_uncert', 'mr_noc_decode_batched', 'mr_pnp_from_head_batched', 'mr_nms_bev_batched', 'mr_bbox3d_overlaps_aligned', 'pnp_noc_uncert', 'pnp_noc_cov_uncert', 'mr_pnp_noc_batched',
                     'mr_kitti_overlaps', 'mr_kitti_match_workspace_bytes', 'mr_kitti_match', 'mr_roi_align_avg')

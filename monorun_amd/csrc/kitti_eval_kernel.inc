@@ -19,8 +19,17 @@ __device__ __forceinline__ double t_max(double a, double b) { return fmax(a, b);
 __device__ __forceinline__ float t_min(float a, float b) { return fminf(a, b); }
 __device__ __forceinline__ double t_min(double a, double b) { return fmin(a, b); }
 
-// Cyrus-Beck clipped boundary integral (see edge_inside_area above), any scalar type.
-template <typename T, bool CLOSED>
+// a*b + c*d rounded operation by operation, never fused into an FMA
+template <typename T>
+__device__ __forceinline__ T dot2_unfused(T a, T b, T c, T d) {
+#pragma clang fp contract(off)
+    return a * b + c * d;
+}
+
+// Cyrus-Beck clipped boundary integral (see edge_inside_area above), any scalar type.  UNFUSED (the 3-D IoU, iou3d_kernel.inc): the
+// two dot products are not contracted, so that an edge lying on the other box's edge (identical boxes) gives den == 0 and f0 == 0
+// exactly and the shared edge is counted once; the default (the KITTI evaluator) compiles as it always has.
+template <typename T, bool CLOSED, bool UNFUSED = false>
 __device__ __forceinline__ T edge_inside_area_t(T px, T py, T dx, T dy, const T (&qx)[4], const T (&qy)[4]) {
     T t0 = T(0), t1 = T(1);
     bool empty = false;
@@ -28,8 +37,9 @@ __device__ __forceinline__ T edge_inside_area_t(T px, T py, T dx, T dy, const T 
     for (int e = 0; e < 4; ++e) {
         const T ax = qx[e], ay = qy[e], bx = qx[(e + 1) & 3], by = qy[(e + 1) & 3];
         const T nx = -(by - ay), ny = bx - ax;
-        const T f0 = nx * (px - ax) + ny * (py - ay);
-        const T den = nx * dx + ny * dy;
+        T f0, den;
+        if constexpr (UNFUSED) { f0 = dot2_unfused(nx, px - ax, ny, py - ay); den = dot2_unfused(nx, dx, ny, dy); }
+        else { f0 = nx * (px - ax) + ny * (py - ay); den = nx * dx + ny * dy; }
         if (den > T(0)) t0 = t_max(t0, -f0 / den);
         else if (den < T(0)) t1 = t_min(t1, -f0 / den);
         else if (CLOSED ? (f0 < T(0)) : (f0 <= T(0))) empty = true;
@@ -50,6 +60,7 @@ __device__ __forceinline__ void eval_corners(const double (&b)[5], double ox, do
     if (hx * hy < 0.0) { const double tx = px[1], ty = py[1]; px[1] = px[3]; py[1] = py[3]; px[3] = tx; py[3] = ty; }
 }
 
+template <bool UNFUSED = false>
 __device__ __forceinline__ double eval_rotated_intersection(const double (&a)[5], const double (&b)[5]) {
     double ax[4], ay[4], bx[4], by[4];
     eval_corners(a, a[0], a[1], ax, ay);
@@ -57,8 +68,8 @@ __device__ __forceinline__ double eval_rotated_intersection(const double (&a)[5]
     double ov = 0.0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        ov += edge_inside_area_t<double, true>(ax[i], ay[i], ax[(i + 1) & 3] - ax[i], ay[(i + 1) & 3] - ay[i], bx, by);
-        ov += edge_inside_area_t<double, false>(bx[i], by[i], bx[(i + 1) & 3] - bx[i], by[(i + 1) & 3] - by[i], ax, ay);
+        ov += edge_inside_area_t<double, true, UNFUSED>(ax[i], ay[i], ax[(i + 1) & 3] - ax[i], ay[(i + 1) & 3] - ay[i], bx, by);
+        ov += edge_inside_area_t<double, false, UNFUSED>(bx[i], by[i], bx[(i + 1) & 3] - bx[i], by[(i + 1) & 3] - by[i], ax, ay);
     }
     return fmax(ov, 0.0);
 }

@@ -775,6 +775,7 @@ __global__ void __launch_bounds__(64) cov_symeig_rule_kernel(uint8_t *valid, flo
 }
 
 #include "kitti_eval_kernel.inc"
+#include "iou3d_kernel.inc"
 
 size_t lds_bytes(const PnpArgs &a, int wpo) {
     size_t n = 0;
@@ -1717,6 +1718,20 @@ int mr_nms_bev_batched(const float *boxes_xyxyr, const float *scores, const int3
     const size_t lds = (size_t)np2 * 8 + (size_t)max_group * sizeof(NmsBox) + (size_t)max_group * ((max_group + 31) / 32) * 4 + 16;
     hipLaunchKernelGGL(nms_bev_kernel, dim3(groups), dim3(256), lds, (hipStream_t)stream, boxes_xyxyr, scores, (const int *)offsets, thr,
                        (long long *)keep, (int *)num_keep);
+    HIP_TRY(hipGetLastError());
+    return MR_OK;
+}
+
+// ---- N5: aligned rotated 3-D IoU (bbox3d_iou_calculator.py:166-192)
+int mr_bbox3d_overlaps_aligned(const float *boxes, int64_t boxes_row_stride, const float *qboxes, int64_t qboxes_row_stride, int n,
+                               int criterion, int z_axis, float z_center, int flags, float *iou, float *rinc, void *stream) {
+    if (n < 0 || criterion < -1 || criterion > 2 || z_axis < 0 || z_axis > 2 || (flags & ~MR_IOU3D_GEOMETRIC_HEIGHT)) return MR_ERR_BAD_ARGUMENT;
+    if (boxes_row_stride < 7 || qboxes_row_stride < 7) return MR_ERR_BAD_ARGUMENT;
+    if (n == 0) return MR_OK;
+    if (!boxes || !qboxes || !iou) return MR_ERR_BAD_ARGUMENT;
+    hipLaunchKernelGGL(bbox3d_overlaps_aligned_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, boxes,
+                       (long long)boxes_row_stride, qboxes, (long long)qboxes_row_stride, n, criterion, z_axis, z_center,
+                       (flags & MR_IOU3D_GEOMETRIC_HEIGHT) ? 1 : 0, iou, rinc);
     HIP_TRY(hipGetLastError());
     return MR_OK;
 }

@@ -4,9 +4,9 @@
     (fcn_noc_decoder.py:225-267, multiclass_norm_dim_coder.py:28-36, noc_coder.py:50-73,
     distance_invar_proj_error_coder.py:39-60, uncert_prop_pnp_optimizer.py:73,86-88,
     roi_align(coord_2d) at monorun_roi_head.py:521-523)
-  * ``UncertPropPnPOptimizer`` — same constructor / ``forward`` contract as
-    /root/reference/monorun/models/roi_heads/bbox_3d_heads/optimizers/uncert_prop_pnp_optimizer.py:12-99
-    (losses are training-only and out of scope: SURVEY.md §8)
+  * ``UncertPropPnPOptimizer`` — same constructor / ``forward`` / ``get_targets`` / ``loss`` contract as
+    the reference's monorun/models/roi_heads/bbox_3d_heads/optimizers/uncert_prop_pnp_optimizer.py:12-159
+    (the loss's 3-D IoU is the HIP kernel of ``iou3d``, its losses are torch: ``losses``)
   * ``cov_correction`` — R13 (distance_invar_proj_error_coder.py:62-63 with the 'range' distance of
     uncert_projection_head.py:104-109), applied at monorun_roi_head.py:530-534
   * ``pnp_from_head`` / ``pose_from_head`` — the whole post-NOC-head tail in ONE launch (K2 fused into the PnP kernel's
@@ -19,6 +19,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .iou3d import bbox3d_overlaps_aligned
+from .losses import build_loss
 from .ops import build_pnp
 
 # coder constants of the shipped configs (configs/kitti_multiclass.py / kitti_car.py; coder defaults)
@@ -393,9 +395,21 @@ def cov_correction(cov, t_vec, ref_length=1.6, ref_focal_y=722, target_std=0.15)
     return cov * (sd / torch.norm(t_vec, p=2, dim=1)).square().view(-1, 1, 1)
 
 
+class Vec2DRotationCoder:
+    """yaw (n, 1) -> (cos, sin) (n, 2) (the reference's core/bbox_3d/rotation_coder/vec2d_rotation_coder.py)."""
+
+    @staticmethod
+    def encode(angles):
+        if angles.dim() == 1:
+            angles = angles.unsqueeze(-1)
+        return torch.cat((torch.cos(angles), torch.sin(angles)), dim=-1)
+
+
 class UncertPropPnPOptimizer(nn.Module):
-    """Pose head (inference).  Constructor keywords follow the reference so that the ``pose_head`` dict
-    of the shipped configs builds unchanged; loss dicts are accepted and ignored."""
+    """Pose head.  Constructor keywords follow the reference so that the ``pose_head`` dict of the shipped configs builds unchanged.
+    Loss dicts are built as the reference builds them (``losses.build_loss``: mmdet's registry when it imports, else this package's)
+    and stay plain assignable attributes, as ``LossUpdaterHook`` expects; a type no registry knows raises only when ``loss()``
+    calls it.  The losses add no parameters or buffers: ``state_dict()`` is that of the inference head."""
 
     def __init__(self, loss_rot=None, loss_trans=None, loss_calib=None,
                  rotation_coder=dict(type='Vec2DRotationCoder'),
@@ -404,6 +418,11 @@ class UncertPropPnPOptimizer(nn.Module):
                  allowed_border=200, epnp_ransac_thres_ratio=0.2, std_scale=10):
         super().__init__()
         self.pnp = build_pnp(pnp)
+        self.rotation_coder = Vec2DRotationCoder() if (rotation_coder or {}).get('type') == 'Vec2DRotationCoder' else None
+        self.rotation_coder_cfg = rotation_coder
+        self.loss_rot = build_loss(loss_rot)
+        self.loss_trans = build_loss(loss_trans)
+        self.loss_calib = build_loss(loss_calib)
         if getattr(self.pnp, 'use_6dof', False):
             # the reference never reads this flag (pnp_uncert.py:11): inside the head the pose stays [yaw, t] with a 4x4 covariance
             # (calibration and score head are 4-DoF); the real 6-DoF refinement is ops.pnp_uncert(..., use_6dof=True)
@@ -459,6 +478,55 @@ class UncertPropPnPOptimizer(nn.Module):
                                                     dec['ransac_thr'])
         out = (ret_val, yaw, t_vec, pose_cov, self._calibrate(pose_cov))
         return out + (mask,) if with_mask else out
+
+    def get_targets(self, pos_bboxes_3d):
+        """pos_bboxes_3d (n, 7) [l, h, w, x, y, z, ry] -> yaw_targets (n, 1), trans_targets (n, 3)."""
+        return pos_bboxes_3d[:, 6:7], pos_bboxes_3d[:, 3:6]
+
+    def loss(self, ret_val, yaw_pred, t_vec_pred, pose_cov, dimensions_pred, yaw_targets, trans_targets, pos_bboxes_3d, eps=1e-6):
+        """The reference's pose loss (uncert_prop_pnp_optimizer.py:106-159).
+
+        Args:
+            ret_val (n,) bool, yaw_pred (n, 1), t_vec_pred (n, 3), pose_cov (n, 4, 4) (the calibrated covariance, as the RoI head
+            passes it), dimensions_pred (n, 3), yaw_targets (n, 1), trans_targets (n, 3), pos_bboxes_3d (n, 7) [l, h, w, x, y, z, ry]
+
+        Returns:
+            (dict with 'mean_iou' and, for each loss module the head has, 'loss_rot' / 'loss_trans' / 'loss_calib';
+             ious (n, 1): the 3-D IoU of predicted and target box, no grad, 0 for invalid objects — the score head's target)
+        """
+        half = (torch.float16, torch.bfloat16)
+        yaw_pred, t_vec_pred, pose_cov, dimensions_pred = (t.float() if t.dtype in half else t for t in (yaw_pred, t_vec_pred, pose_cov, dimensions_pred))
+        ret_val = ret_val.reshape(-1).bool()
+        loss_pose = dict()
+        with torch.no_grad():
+            ious = bbox3d_overlaps_aligned(pos_bboxes_3d[:, [3, 4, 5, 0, 1, 2, 6]], torch.cat((t_vec_pred, dimensions_pred, yaw_pred), dim=1))
+            ious[~ret_val] = 0
+        loss_pose['mean_iou'] = ious.sum() if ious.size(0) == 0 else ious.mean()
+
+        yaw_pred, yaw_targets = yaw_pred[ret_val], yaw_targets[ret_val]
+        t_vec_pred, trans_targets = t_vec_pred[ret_val], trans_targets[ret_val]
+        pose_cov = pose_cov[ret_val]
+        if self.loss_rot is not None:
+            if self.rotation_coder is None:
+                raise RuntimeError(f'UncertPropPnPOptimizer.loss: loss_rot needs a Vec2DRotationCoder, got {self.rotation_coder_cfg!r}')
+            rot_pred = self.rotation_coder.encode(yaw_pred)
+            rot_targets = self.rotation_coder.encode(yaw_targets)
+            if rot_pred.size(0) == 0:
+                loss_pose['loss_rot'] = rot_pred.sum()
+            else:
+                loss_pose['loss_rot'] = self.loss_rot(torch.norm(rot_pred - rot_targets, dim=1, p=2, keepdim=True), -1)
+        if self.loss_trans is not None:
+            loss_pose['loss_trans'] = t_vec_pred.sum() if t_vec_pred.size(0) == 0 else self.loss_trans(t_vec_pred, trans_targets)
+        if self.loss_calib is not None:
+            if pose_cov.size(0) == 0:
+                loss_pose['loss_calib'] = pose_cov.sum()
+            else:
+                with torch.no_grad():
+                    yaw_diff = ((yaw_pred - yaw_targets) + np.pi) % (2 * np.pi) - np.pi
+                    diff = torch.cat([yaw_diff, t_vec_pred - trans_targets], dim=1)
+                inv_cov = torch.inverse(pose_cov + torch.eye(pose_cov.size(-1), dtype=pose_cov.dtype, device=pose_cov.device))
+                loss_pose['loss_calib'] = self.loss_calib(diff, 0, inv_cov=inv_cov)
+        return loss_pose, ious
 
 
 def pose_from_head(pose_head, all_pred, labels, flip, dim, dim_var, rois, cam_intrinsic, img_shape,
