@@ -17,11 +17,12 @@
     unsigned long long *sball = (unsigned long long *)(shyp + 30 * 12);      // [nca]
     int *scnt = (int *)(sball + a.nca);                                      // [4][32] (+4)
     unsigned char *tile_base = (unsigned char *)(scnt + 4 * 32 + 4);
-    Tile<T> tl;
-    tl.ra = (const T *)tile_base; tl.rb = (const T *)tile_base + (size_t)4 * P;
-    uint16_t *slist = (uint16_t *)(tile_base + (size_t)8 * P * sizeof(T));
-    uint16_t *slist2 = slist + ((P + 7) & ~7);
-    uint8_t *smask = (uint8_t *)(slist2 + ((P + 7) & ~7));
+    const int np = (P + 7) & ~7;
+    GeoTile<T> tl;
+    tl.r = (const T *)tile_base; tl.np = np;
+    uint16_t *slist = (uint16_t *)(tile_base + (size_t)5 * np * sizeof(T));
+    uint16_t *slist2 = slist + np;
+    unsigned *smask = (unsigned *)(slist2 + np);                            // [(P + 31) / 32]: the inlier mask, one bit per point
 
     const EpCallView cv = ep_call_view(ea, b);
     ep_load_geometry<T>(cv, b, P, NT, tl);
@@ -33,7 +34,7 @@
     const bool use_ransac_refit_f64 = cv.ransac_thr != nullptr && !(a.flags & MR_EPNP_REFIT_F32) &&
                                       !((a.flags & MR_EPNP_CV_EARLY_RETURN) && mode == EP_MODE_PLAIN && n == 5);
     auto fetch = [&](int q, float (&o)[3], float (&im)[2]) {          // point index -> float32 correspondence
-        typename Tile<T>::Raw r;
+        typename GeoTile<T>::Raw r;
         tl.load(q, r);
         o[0] = (float)to_f(r.x); o[1] = (float)to_f(r.y); o[2] = (float)to_f(r.z); im[0] = (float)to_f(r.u); im[1] = (float)to_f(r.v);
     };
@@ -53,7 +54,7 @@
             for (int i = 0; i < 12; ++i) shyp[tid * 12 + i] = ea.w.hrt[i * nq + q];
         }
         for (int i = tid; i < 4 * 32; i += NT) scnt[i] = 0;
-        for (int p = tid; p < P; p += NT) smask[p] = 0;
+        for (int i = tid; i < (P + 31) >> 5; i += NT) smask[i] = 0u;
         __syncthreads();
 #if defined(EP_CONS_EXIT) && EP_CONS_EXIT == 1
         return;
@@ -108,6 +109,16 @@
         iters_run = it;
         if (it < niters && ea.h1 < kEpMaxIters) {                  // the loop goes on: the remaining hypotheses are solved in the next round
             if (tid == 0) { meta[EP_M_PENDING] = 1; meta[EP_M_NITERS] = niters; meta[EP_M_BEST] = best; meta[EP_M_BESTH] = besth; meta[EP_M_ITERS] = it; }
+            // ... on the samples of the hypotheses [h1, niters), which the front launch left to this one: their correspondences from the
+            // tile (the float32 values ep_fetch_global returns) -> the workspace's sample records, as the front launch writes [0, h1)
+            const uint16_t *spt = ea.w.spt + (long long)b * (5 * kEpMaxIters);
+            for (int k = 5 * ea.h1 + tid; k < 5 * niters; k += NT) {
+                const int h = k / 5, i = k - 5 * h;
+                float o[3], im[2];
+                fetch((int)spt[k], o, im);
+                float *s = ea.w.samp + ((long long)b * kEpMaxIters + h) * kEpSampRec + 5 * i;
+                s[0] = o[0]; s[1] = o[1]; s[2] = o[2]; s[3] = im[0]; s[4] = im[1];
+            }
             return;
         }
         if (best <= 0) ok = false;
@@ -126,7 +137,7 @@
                 float o[3], im[2];
                 fetch(pidx, o, im);
                 const bool in = lvq && ep_is_inlier(cam, R, t, o[0], o[1], o[2], im[0], im[1], thr2);
-                if (lvq) smask[pidx] = in ? 1 : 0;
+                if (in) atomicOr(&smask[pidx >> 5], 1u << (pidx & 31));
                 const unsigned long long bal = __ballot(in);
                 if (lane == 0 && i * WPO + wid < nlc) sball[i * WPO + wid] = bal;
             }
@@ -142,7 +153,7 @@
             }
             list = slist2;
             __syncthreads();
-            for (int p = tid; p < P; p += NT) cv.init_mask[(long long)b * P + p] = smask[p];
+            for (int p = tid; p < P; p += NT) cv.init_mask[(long long)b * P + p] = (uint8_t)((smask[p >> 5] >> (p & 31)) & 1u);
         }
     } else __syncthreads();
 #if defined(EP_CONS_EXIT) && EP_CONS_EXIT == 3
@@ -205,7 +216,7 @@
         for (int i = 0; i < 9; ++i) ci[i] = uni(sprep[12 + i]);
         EpCam camu;
         camu.fx = uni(cam.fx); camu.fy = uni(cam.fy); camu.cx = uni(cam.cx); camu.cy = uni(cam.cy);
-        const EpRefitPoint<T> point{ tl, list, camu, cws, ci, uni(1.0 / cam.fx), uni(1.0 / cam.fy), use_ransac_refit_f64 };
+        const EpRefitPoint<T, GeoTile<T>> point{ tl, list, camu, cws, ci, uni(1.0 / cam.fx), uni(1.0 / cam.fy), use_ransac_refit_f64 };
         // B) M^T M: wave w owns the entries k = w mod 4 of the upper triangle
         double acc[12], ext[5], afirst[4];
         const double pw0[3] = { cws[0][0], cws[0][1], cws[0][2] };

@@ -5,14 +5,15 @@
 // 677 spills, two sequential eigen-solves of 250 us each with one active lane-group per workgroup).
 //
 //   front      one workgroup per object: records -> LDS, istd candidates (numpy's float32 summation order), the 30 five-point
-//              subsets of cv::RNG((uint64)-1) (they do not depend on any model), the samples' correspondences -> workspace
+//              subsets of cv::RNG((uint64)-1) (they do not depend on any model), their point indices and the first round's
+//              samples' correspondences -> workspace
 //   hyp        one QUAD per hypothesis of the round, everything in registers: control points, barycentric coordinates, M^T M (each lane
 //              its rows), the four eigenvectors (epnp_eig_low4.inc), then lanes 0..2 = the beta candidates N = 1, 2, 3 on one code
 //              path: approximation, Gauss-Newton, pose, reprojection error of each candidate -> workspace
 //   consensus  one workgroup per object: the best candidate of every hypothesis through the Rodrigues round trip of solvePnP's
 //              output, float32 reprojection test of all candidates against the round's hypotheses, OpenCV's
 //              sequential loop replayed over the counts in RNG order, the winner's inlier mask / list, and the point sums of the
-//              re-fit (centroid, PCA, M^T M)
+//              re-fit (centroid, PCA, M^T M); an object whose loop goes on: the correspondences of its second round's samples
 //   refit_betas one quad per object: the re-fit's four eigenvectors, then lanes 0..2 = the beta candidates: the candidates' control
 //              points in the camera frame
 //   refit      one workgroup per object, one wave per candidate: the point sums (the waves' butterflies), pose and reprojection
@@ -32,7 +33,9 @@ enum { EP_MODE_FAIL = 0, EP_MODE_PLAIN = 1, EP_MODE_RANSAC = 2 };
 struct EpnpWork {
     int *meta;            // [B][kEpMeta]: candidates, mode, points of the re-fit, re-fit wanted, iterations run, best count, best model,
                           //               second round wanted, the loop's current iteration bound
-    float *samp;          // [NQ][28]: the five correspondences of every sample (X Y Z u v per point; 25 floats in a 112-byte record), NQ = 30 B
+    float *samp;          // [NQ][28]: the five correspondences of every sample (X Y Z u v per point; 25 floats in a 112-byte record), NQ = 30 B;
+                          //           the front launch writes the first round's, the consensus launch those a pending object's second round solves
+    uint16_t *spt;        // [B][150]: the point index of every sample's five correspondences
     double *hrt;          // [12][NQ]: R (row-major, after the Rodrigues round trip) | t of every hypothesis' best beta candidate
     uint16_t *cand;       // [B][pstride] ascending candidate list
     uint16_t *fit;        // [B][pstride] the re-fit's point list
@@ -77,10 +80,12 @@ size_t epnp_work_bytes(int B, int P, EpnpWork *w, unsigned char *base) {
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_meta = take(sizeof(int) * kEpMeta * B), o_samp = take(sizeof(float) * kEpSampRec * nq), o_hrt = take(sizeof(double) * 12 * nq),
                  o_cand = take(sizeof(uint16_t) * ps * B), o_fit = take(sizeof(uint16_t) * ps * B), o_prep_r = take(sizeof(double) * 24 * B),
-                 o_mtm_r = take(sizeof(double) * 144 * B), o_ccs_r = take(sizeof(double) * 36 * B), o_cam = take(sizeof(float) * 4 * B), o_abt_r = take(sizeof(double) * 24 * B);
+                 o_mtm_r = take(sizeof(double) * 144 * B), o_ccs_r = take(sizeof(double) * 36 * B), o_cam = take(sizeof(float) * 4 * B), o_abt_r = take(sizeof(double) * 24 * B),
+                 o_spt = take(sizeof(uint16_t) * 5 * kEpMaxIters * B);
     if (w) {
         w->meta = (int *)(base + o_meta); w->samp = (float *)(base + o_samp); w->hrt = (double *)(base + o_hrt); w->cand = (uint16_t *)(base + o_cand);
         w->fit = (uint16_t *)(base + o_fit); w->prep_r = (double *)(base + o_prep_r); w->mtm_r = (double *)(base + o_mtm_r); w->ccs_r = (double *)(base + o_ccs_r); w->cam = (float *)(base + o_cam); w->abt_r = (double *)(base + o_abt_r);
+        w->spt = (uint16_t *)(base + o_spt);
         w->nq = (long long)nq; w->pstride = (int)ps;
     }
     return off;
@@ -115,8 +120,9 @@ __device__ __forceinline__ EpCam ep_cam_of(const EpCallView &a, int b) {
 }
 // What a stage needs of an object's correspondences, and no more (HBM traffic of one call: 5.4 x the algorithmic bytes with every
 // workgroup-per-object launch loading all seven channel rows, profiles/r05a_epnp_traffic.json): the front launch tests the WEIGHTS
-// (two rows; A records {0, 0, wu, wv}, no B records) and fetches the 150 sampled correspondences straight from global memory; the
-// consensus and re-fit launches read the GEOMETRY (five rows; A records {u, v, 0, 0}).  Same record layout as load_records.
+// (two rows; A records {0, 0, wu, wv}, no B records) and fetches the first round's sampled correspondences straight from global memory
+// (the consensus launch writes a pending object's others from its tile); the consensus launch reads the GEOMETRY into a GeoTile (five
+// planar rows), the re-fit launch into Tile's records (A records {u, v, 0, 0}, same layout as load_records).
 template <typename T>
 __device__ __forceinline__ void ep_load_weights(const EpCallView &a, int b, int P, int NT, const Tile<T> &tl) {
     const T *gw = (const T *)a.istd + (long long)b * a.sw[0];
@@ -138,6 +144,29 @@ __device__ __forceinline__ void ep_load_geometry(const EpCallView &a, int b, int
         ra_.e[0] = g2[(long long)p * a.s2[1]]; ra_.e[1] = g2[(long long)p * a.s2[1] + a.s2[2]]; ra_.e[2] = ra_.e[3] = T(0.0f);
         rb_.e[0] = g3[(long long)p * a.s3[1]]; rb_.e[1] = g3[(long long)p * a.s3[1] + a.s3[2]]; rb_.e[2] = g3[(long long)p * a.s3[1] + 2 * a.s3[2]]; rb_.e[3] = T(0.0f);
         wa[p] = ra_; wb[p] = rb_;
+    }
+}
+// The consensus launch's geometry tile: five planar rows x, y, z, u, v of np = P rounded up to 8 entries each, in the storage type —
+// 20 B per point at fp32 where Tile's two 16-byte records {u, v, 0, 0} {x, y, z, 0} take 32 (15.7 instead of 25.1 KB at P = 784).  A
+// wave's reads of a row at consecutive points are 4-byte reads of consecutive words (conflict-free); load() hands out the same raw values.
+template <typename T>
+struct GeoTile {
+    const T *r; int np;
+    using Raw = TileRaw<T>;
+    __device__ __forceinline__ void load(int p, Raw &o) const {
+        o.x = r[p]; o.y = r[np + p]; o.z = r[2 * np + p]; o.u = r[3 * np + p]; o.v = r[4 * np + p];
+    }
+};
+template <typename T>
+__device__ __forceinline__ void ep_load_geometry(const EpCallView &a, int b, int P, int NT, const GeoTile<T> &tl) {
+    const T *g2 = (const T *)a.x2d + (long long)b * a.s2[0];
+    const T *g3 = (const T *)a.x3d + (long long)b * a.s3[0];
+    T *w = const_cast<T *>(tl.r);
+    const int np = tl.np;
+    for (int p = threadIdx.x; p < P; p += NT) {
+        const T x = g3[(long long)p * a.s3[1]], y = g3[(long long)p * a.s3[1] + a.s3[2]], z = g3[(long long)p * a.s3[1] + 2 * a.s3[2]];
+        const T u = g2[(long long)p * a.s2[1]], v = g2[(long long)p * a.s2[1] + a.s2[2]];
+        w[p] = x; w[np + p] = y; w[2 * np + p] = z; w[3 * np + p] = u; w[4 * np + p] = v;
     }
 }
 // one correspondence straight from global memory, as the float32 values the tile would hand out
@@ -558,11 +587,15 @@ __global__ void __launch_bounds__(kEpThreads) epnp_front_kernel(const EpnpStageA
         __syncthreads();
         if (tid < 5 * kEpMaxIters) {                     // thread (h, i): correspondence i of sample h -> workspace
             const int h = tid / 5, i = tid - 5 * h;
-            float o[5];
-            ep_fetch_global<T>(cv, b, (int)slist[sidx[tid]], o);
-            const long long q = (long long)b * kEpMaxIters + h;
-            float *s = ea.w.samp + q * kEpSampRec + 5 * i;
-            s[0] = o[0]; s[1] = o[1]; s[2] = o[2]; s[3] = o[3]; s[4] = o[4];
+            const int p = (int)slist[sidx[tid]];
+            ea.w.spt[(long long)b * (5 * kEpMaxIters) + tid] = (uint16_t)p;
+            if (h < ea.h1) {                             // the first round's samples; a pending object's consensus launch writes the rest
+                float o[5];
+                ep_fetch_global<T>(cv, b, p, o);
+                const long long q = (long long)b * kEpMaxIters + h;
+                float *s = ea.w.samp + q * kEpSampRec + 5 * i;
+                s[0] = o[0]; s[1] = o[1]; s[2] = o[2]; s[3] = o[3]; s[4] = o[4];
+            }
         }
     }
     if (mode != EP_MODE_FAIL) for (int i = tid; i < n; i += NT) ea.w.cand[(long long)b * ea.w.pstride + i] = slist[i];
@@ -609,9 +642,10 @@ constexpr int kEpPoseThreads = 192;     // the re-fit's workgroup: one wave per 
 #define EP_EIG_STAMPS nullptr
 #endif
 #ifndef MR_EP_CONS_WAVES
-#define MR_EP_CONS_WAVES 4       // waves per SIMD the consensus launch is compiled for: 4 = 111 registers, NO scratch (the default since round 6: VERDICT r5 item 5); 5 = 96 registers with
-                                 // 7 spilled (32 B of scratch per lane), five objects per CU by registers and by LDS.  Same speed one call at a time (263.6 | 263.0 us per 1024-object
-                                 // call) and with launch sets in flight (10.67 | 10.64 M solves/s, sets of five on four streams; round 5: 10.33 -> 10.52 with sets of three) — profiles/r06_cons_waves.txt
+#define MR_EP_CONS_WAVES 5       // waves per SIMD the consensus launch is compiled for: 5 = 96 registers with 7 spilled (32 B of scratch per lane, all of it in wave 0's control-point
+                                 // block: ep_eig3), five objects per CU by registers and 5 x 21.9 KB of LDS, which leaves 50 KB of the CU to the other streams' workgroups; 4 = 105
+                                 // registers, no scratch.  Sets of five on four streams, eight fresh processes each, alternating: 12.30 | 11.91 M solves/s (main: 11.75); in flight
+                                 // the LM launch is resident 460 | 514 us (539) — profiles/r07_bench_ab.txt, r07_inflight_trace.txt.  Round 6 (31.8 KB tile): same speed either way
 #endif
 #ifndef MR_EP_REFIT_WAVES
 #define MR_EP_REFIT_WAVES 4
@@ -633,7 +667,8 @@ __device__ __forceinline__ void ep_load_sample(const EpnpStageArgs &ea, const lo
     }
 }
 
-// one hypothesis q of object b by the quad this lane belongs to; sqcol = the quad's scratch column (slot s at sqcol[16 s])
+// one hypothesis q of object b by the quad this lane belongs to; sqcol = the quad's scratch column (slot s at sqcol[16 s]).
+// epnp_round2_kernel calls this in a branch only some of its waves take: it must contain no block barrier and no static shared memory.
 template <int LV = 0>
 __device__ __forceinline__ void ep_hyp_body(const EpnpStageArgs &ea, const int b, const long long q, double *sqcol, const int sqi = 0, double *wide = nullptr) {
     MR_EXACT
@@ -837,14 +872,15 @@ __global__ void __launch_bounds__(64, MR_EP_QUAD_WAVES) epnp_hyp_kernel(const Ep
 }
 
 // ------------------------------------------------------------------------------------------------ consensus + the re-fit's sums
-size_t epnp_consensus_lds_bytes(const PnpArgs &a) {
+size_t epnp_consensus_lds_bytes(const PnpArgs &a) {      // 21.9 KB at P = 784, fp32 (round 6: 31.8)
+    const size_t np = (size_t)((a.P + 7) & ~7);
     size_t n = 0;
     n += sizeof(double) * (30 * 12);
     n += sizeof(unsigned long long) * a.nca;
     n += sizeof(int) * (4 * 32 + 4);
-    n += (size_t)8 * a.P * a.elem_size;
-    n += 2 * sizeof(uint16_t) * ((a.P + 7) & ~7);
-    n += (a.P + 15) & ~15;
+    n += 5 * np * a.elem_size;                            // GeoTile
+    n += 2 * sizeof(uint16_t) * np;
+    n += sizeof(unsigned) * ((a.P + 31) >> 5);             // inlier mask, one bit per point
     return (n + 15) & ~(size_t)15;
 }
 
@@ -887,8 +923,8 @@ struct EpRefitPoint {
 // sum a_j (4), sum a_j (pw - pw0) (4 x 3) and sum (pw - pw0) (3) — wave W: control point W's four sums and component W of the last —
 // instead of two passes over the inliers per candidate; ext = { sum a_W, sum a_W q_0, sum a_W q_1, sum a_W q_2, sum q_W (W < 3) },
 // afirst = the first inlier's coordinates (lane 0 of wave 0: the sign test of the candidates' first camera-frame point).
-template <int W, typename T>
-__device__ __forceinline__ void ep_mtm_part(const EpRefitPoint<T> &point, const EpCam &camu, const double (&pw0)[3], const int nn, const int lane,
+template <int W, typename T, typename TL>
+__device__ __forceinline__ void ep_mtm_part(const EpRefitPoint<T, TL> &point, const EpCam &camu, const double (&pw0)[3], const int nn, const int lane,
                                             double (&acc)[12], double (&ext)[5], double (&afirst)[4]) {
     MR_EXACT
     constexpr int NP = W < 2 ? 3 : 2;                     // pairs W, W + 4 (, W + 8)

@@ -1104,11 +1104,12 @@ int launch_epnp_stages(EpnpStageArgs &ea, void *workspace, size_t workspace_byte
         const int cons_wpo = cons_env ? cons_env : 4;
         if ((r = grant_lds(cons_wpo == 2 ? (const void *)epnp_consensus_kernel<T, 2> : (const void *)epnp_consensus_kernel<T, 4>, lds_c)) != MR_OK) return r;
         if ((r = grant_lds((const void *)epnp_refit_kernel<T>, lds_r)) != MR_OK) return r;
-        hipLaunchKernelGGL((epnp_front_kernel<T>), dim3(a.B), dim3(kEpThreads), lds_f, st, ea);
         // The 30 hypotheses of an object are solved in two rounds: [0, first) for every object, the rest only for the objects whose
         // replayed loop still wants iterations after `first` (ptsetreg.cpp's adaptive bound: with few outliers it drops to a
         // handful after the first good model — config-2 batches: 1.5 iterations on average, 8 at most).  Same results either way.
         const int first = first_round < 1 ? 1 : (first_round > kEpMaxIters ? kEpMaxIters : first_round);
+        ea.h0 = 0; ea.h1 = first;                             // the front launch fetches the samples of the first round only
+        hipLaunchKernelGGL((epnp_front_kernel<T>), dim3(a.B), dim3(kEpThreads), lds_f, st, ea);
         // small launch sets (one call at a time): the second round as ONE launch (epnp_round2_kernel); launch sets in flight keep the two compact ones
         // development / tests: force the quads per matrix (0, 2 or 4 levels) of both lane-mapped launches (MR_EP_WIDE) or of one (MR_EP_WIDE_HYP, MR_EP_WIDE_BETAS)
         static const auto lv_env = [](const char *name) { const char *e = getenv(name); const int v = e ? atoi(e) : -1; return (v == 0 || v == 2 || v == 4) ? v : -1; };
