@@ -414,6 +414,45 @@ int mr_bbox3d_overlaps_aligned(const float *boxes, int64_t boxes_row_stride, con
                                int criterion, int z_axis, float z_center, int flags, float *iou, float *rinc, void *stream);
 
 /*
+ * N6: the NOC head's training loss — UncertProjectionHead.forward and RobustKLLoss of the reference
+ * (monorun/models/roi_heads/bbox_3d_heads/reprojection_heads/uncert_projection_head.py:36-79,
+ * monorun/models/losses/robust_kl_loss.py:6-30), forward and backward.  All pointers are device fp32 buffers, contiguous.
+ *
+ * mr_uncert_projection: coords_3d (n,3,hw) object coordinates, pose (n,4) [x, y, z, yaw] (row i at pose + i * pose_row_stride,
+ *   stride in elements, >= 4), cam_intrinsic (n,3,3), img_shapes (n,2) [H, W] -> coords_2d (n,2,hw): uv = (K R_y(yaw) X + K t)[:2] / clamp(z, min=z_min), then clamp(min=-allowed_border) and
+ *   min(., [W, H] + allowed_border).  sin / cos of yaw in fp64 rounded to fp32, the products in fp32, dot products left to right
+ *   without contraction, IEEE division; NaN propagates through the clamps and the min as in torch.  One thread per pixel.
+ * mr_uncert_projection_backward: grad_coords_2d (n,2,hw) -> grad_coords_3d (n,3,hw) (written, not accumulated), with torch's rules
+ *   at ties (a clamp passes the gradient at its bound, the min gives half to each side).  n = 0 launches nothing.
+ *   Both return MR_ERR_BAD_ARGUMENT for n < 0, hw < 1, a pose row stride below 4 or a NULL pointer.
+ */
+int mr_uncert_projection(const float *coords_3d, const float *pose, int64_t pose_row_stride, const float *cam_intrinsic,
+                         const float *img_shapes, int n, int hw, float z_min, float allowed_border, float *coords_2d, void *stream);
+int mr_uncert_projection_backward(const float *coords_3d, const float *pose, int64_t pose_row_stride, const float *cam_intrinsic,
+                                  const float *img_shapes, int n, int hw, float z_min, float allowed_border, const float *grad_coords_2d,
+                                  float *grad_coords_3d, void *stream);
+
+/*
+ * mr_robust_kl_loss: the reduced robust KL loss of numel elements in two launches (per-workgroup fp64 partial sums into
+ *   workspace, then one workgroup that folds them).  target_mode 0: diff = |pred| (the target 0), -1: diff = pred.
+ *   inv = min(exp(-logstd), 1/eps), dw = diff * inv, raw = (dw < delta ? dw^2 / 2 : delta (dw - delta / 2)) + logstd.
+ *   training != 0 updates *mean_inv_std in place (m = m (1 - momentum) + momentum mean(inv), in fp32 steps).  Then
+ *   c = max(*mean_inv_std, 1e-6) and *loss = loss_weight * (sum or mean of raw / c) (reduction 0 mean, 1 sum); *c_out = c.
+ *   The exp is mr_expf (the decode's specified float32 exp).  The grid depends on numel only and no floating-point atomics are
+ *   used: results are bitwise reproducible.  workspace: >= mr_robust_kl_workspace_bytes(numel) bytes of device memory.
+ * mr_robust_kl_loss_backward: grad_pred and grad_logstd (numel each, written) from the device scalars *grad_loss (upstream) and
+ *   *c (the c_out of the forward), in one launch; it does not read mean_inv_std.
+ *   Both return MR_ERR_BAD_ARGUMENT for numel < 1, another target_mode or reduction, eps <= 0, a NULL pointer or a short workspace.
+ */
+int64_t mr_robust_kl_workspace_bytes(int64_t numel);
+int mr_robust_kl_loss(const float *pred, const float *logstd, int64_t numel, int target_mode, double delta, double eps, double momentum,
+                      int training, int reduction, double loss_weight, float *mean_inv_std, float *loss, float *c_out, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+int mr_robust_kl_loss_backward(const float *pred, const float *logstd, int64_t numel, int target_mode, double delta, double eps,
+                               int reduction, double loss_weight, const float *grad_loss, const float *c, float *grad_pred,
+                               float *grad_logstd, void *stream);
+
+/*
  * N2: KITTI object evaluator, device side — replaces the numba / numba-CUDA code of
  * monorun/core/evaluation/kitti_utils/eval.py and rotate_iou.py.  All arrays are device pointers; images are addressed
  * through exclusive prefix offsets (n_img+1 entries).  Box rows are double[12]:

@@ -35,7 +35,7 @@ def _stale():
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    deps = [SRC, os.path.join(_HERE, "csrc", "pnp_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_kernel_body.inc"), os.path.join(_HERE, "csrc", "pnp6_kernel.inc"), os.path.join(_HERE, "csrc", "hessian_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_backward_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_noc_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_eig_low4.inc"), os.path.join(_HERE, "csrc", "epnp_stages.inc"), os.path.join(_HERE, "csrc", "epnp_consensus_body.inc"), os.path.join(_HERE, "csrc", "kitti_eval_kernel.inc"), os.path.join(_HERE, "csrc", "iou3d_kernel.inc"), os.path.join(INCLUDE, "monorun_pnp.h")]
+    deps = [SRC, os.path.join(_HERE, "csrc", "pnp_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_kernel_body.inc"), os.path.join(_HERE, "csrc", "pnp6_kernel.inc"), os.path.join(_HERE, "csrc", "hessian_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_backward_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_noc_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_eig_low4.inc"), os.path.join(_HERE, "csrc", "epnp_stages.inc"), os.path.join(_HERE, "csrc", "epnp_consensus_body.inc"), os.path.join(_HERE, "csrc", "kitti_eval_kernel.inc"), os.path.join(_HERE, "csrc", "iou3d_kernel.inc"), os.path.join(_HERE, "csrc", "projection_loss_kernel.inc"), os.path.join(INCLUDE, "monorun_pnp.h")]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -137,6 +137,17 @@ def load():
     i64 = ctypes.c_int64
     lib.mr_bbox3d_overlaps_aligned.restype = i32
     lib.mr_bbox3d_overlaps_aligned.argtypes = [vp, i64, vp, i64, i32, i32, i32, f32, i32, vp, vp, vp]
+    lib.mr_uncert_projection.restype = i32
+    lib.mr_uncert_projection.argtypes = [vp, vp, i64, vp, vp, i32, i32, f32, f32, vp, vp]
+    lib.mr_uncert_projection_backward.restype = i32
+    lib.mr_uncert_projection_backward.argtypes = [vp, vp, i64, vp, vp, i32, i32, f32, f32, vp, vp, vp]
+    f64 = ctypes.c_double
+    lib.mr_robust_kl_workspace_bytes.restype = i64
+    lib.mr_robust_kl_workspace_bytes.argtypes = [i64]
+    lib.mr_robust_kl_loss.restype = i32
+    lib.mr_robust_kl_loss.argtypes = [vp, vp, i64, i32, f64, f64, f64, i32, i32, f64, vp, vp, vp, vp, i64, vp]
+    lib.mr_robust_kl_loss_backward.restype = i32
+    lib.mr_robust_kl_loss_backward.argtypes = [vp, vp, i64, i32, f64, f64, i32, f64, vp, vp, vp, vp, vp]
     lib.mr_kitti_overlaps.restype = i32
     lib.mr_kitti_overlaps.argtypes = [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp]
     lib.mr_kitti_match_workspace_bytes.restype = i64
@@ -156,5 +167,5 @@ def check(code):
 
 
 EXPORTED_SYMBOLS = ('mr_pnp_version', 'mr_spin', 'mr_pick_waves', 'mr_pnp_error_string', 'mr_pnp_last_hip_error', 'mr_pnp_device_count',
-                    'mr_pnp_uncert_batched', 'mr_epnp_ransac_batched', 'mr_epnp_ransac_grouped', 'mr_epnp_workspace_bytes', 'mr_pnp_uncert_from_init_batched', 'mr_pnp_uncert_from_init_grouped', 'mr_pnp_uncert_from_epnp_grouped', 'mr_cov_symeig_rule', 'mr_pnp6_refine_batched', 'mr_pnp_exact_hessian_batched', 'mr_pnp_uncert_backward_batched', 'pnp_uncert', 'mr_noc_decode_batched', 'mr_pnp_from_head_batched', 'mr_nms_bev_batched', 'mr_bbox3d_overlaps_aligned', 'pnp_noc_uncert', 'pnp_noc_cov_uncert', 'mr_pnp_noc_batched',
+                    'mr_pnp_uncert_batched', 'mr_epnp_ransac_batched', 'mr_epnp_ransac_grouped', 'mr_epnp_workspace_bytes', 'mr_pnp_uncert_from_init_batched', 'mr_pnp_uncert_from_init_grouped', 'mr_pnp_uncert_from_epnp_grouped', 'mr_cov_symeig_rule', 'mr_pnp6_refine_batched', 'mr_pnp_exact_hessian_batched', 'mr_pnp_uncert_backward_batched', 'pnp_uncert', 'mr_noc_decode_batched', 'mr_pnp_from_head_batched', 'mr_nms_bev_batched', 'mr_bbox3d_overlaps_aligned', 'mr_uncert_projection', 'mr_uncert_projection_backward', 'mr_robust_kl_workspace_bytes', 'mr_robust_kl_loss', 'mr_robust_kl_loss_backward', 'pnp_noc_uncert', 'pnp_noc_cov_uncert', 'mr_pnp_noc_batched',
                     'mr_kitti_overlaps', 'mr_kitti_match_workspace_bytes', 'mr_kitti_match', 'mr_roi_align_avg')

@@ -9,6 +9,9 @@ iteration 100).  It is the negative log-likelihood of the pose error d under N(0
 reduced as mmdet's ``weighted_loss`` reduces ('none' | 'mean' | 'sum', optional element weight and ``avg_factor``) and scaled by
 ``loss_weight``.
 
+``RobustKLLoss`` is the NOC head's projection loss (``loss_proj`` of ``UncertProjectionHead``), the only loss that
+trains the NOC head in the shipped configs with ``loss_noc=None``.  Its reduced forms on CUDA run HIP kernels; the rest runs in torch.
+
 ``build_loss`` builds a loss config dict: with mmdet's registry when mmdet imports and knows the type, else with this module's
 registry.  A type neither knows becomes an ``UnbuiltLoss``, which raises, naming the type, only when it is called.
 """
@@ -70,7 +73,119 @@ class KLLossMV(nn.Module):
         return self.loss_weight * weight_reduce_loss(kl_loss_mv(pred, target, inv_cov), weight, reduction, avg_factor)
 
 
-LOSSES = {'KLLossMV': KLLossMV}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# RobustKLLoss: the NOC head's projection loss, the reference's monorun/models/losses/robust_kl_loss.py.
+
+def robust_kl_loss(pred, target, logstd=None, delta=1.414, momentum=1.0, mean_inv_std=None, eps=1e-4, training=True):
+    """Element-wise robust KL loss, divided by the running mean of the inverse std; in training mode the running mean (the
+    buffer ``mean_inv_std``, 0-dim) is first updated in place.  target: 0 (pred is the error), -1 (pred is the non-negative
+    distance) or a tensor."""
+    if logstd is None or pred.size() != logstd.size():
+        raise ValueError('robust_kl_loss: logstd must be given with the shape of pred')
+    if isinstance(target, int):
+        if target not in (0, -1):
+            raise ValueError(f'robust_kl_loss: an integer target must be 0 or -1, not {target}')
+        diff = pred.abs() if target == 0 else pred
+    else:
+        diff = (pred - target).abs()
+    inv_std = torch.exp(-logstd).clamp(max=1 / eps)
+    dw = diff * inv_std
+    loss = torch.where(dw < delta, 0.5 * dw.square(), delta * (dw - 0.5 * delta)) + logstd
+    if training:
+        with torch.no_grad():
+            mean_inv_std.mul_(1 - momentum)
+            mean_inv_std.add_(momentum * inv_std.detach().mean())
+    return loss / mean_inv_std.clamp(min=1e-6)
+
+
+class _RobustKLFunction(torch.autograd.Function):
+    """Reduced loss in two HIP launches (``mr_robust_kl_loss``), both gradients in one (``mr_robust_kl_loss_backward``).  pred
+    and logstd arrive as contiguous fp32; the buffer is updated on the device, and the divisor c it gave is saved for the
+    backward, which therefore never reads the buffer (it may have moved since) and never waits for the host."""
+
+    @staticmethod
+    def forward(ctx, pred, logstd, buf, mode, delta, eps, momentum, training, reduction, loss_weight):
+        from . import _lib
+        lib = _lib.load()
+        numel = pred.numel()
+        dev = pred.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        c = torch.empty((), device=dev, dtype=torch.float32)
+        ws = torch.empty(int(lib.mr_robust_kl_workspace_bytes(numel)), device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mr_robust_kl_loss(pred.data_ptr(), logstd.data_ptr(), numel, mode, delta, eps, momentum, int(training),
+                                             reduction, loss_weight, buf.data_ptr(), loss.data_ptr(), c.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+        ctx.save_for_backward(pred, logstd, c)
+        ctx.args = (mode, delta, eps, reduction, loss_weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import _lib
+        pred, logstd, c = ctx.saved_tensors
+        mode, delta, eps, reduction, loss_weight = ctx.args
+        grad = grad.to(torch.float32).contiguous()
+        gp, gl = torch.empty_like(pred), torch.empty_like(logstd)
+        dev = pred.device
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().mr_robust_kl_loss_backward(pred.data_ptr(), logstd.data_ptr(), pred.numel(), mode, delta, eps, reduction,
+                                                              loss_weight, grad.data_ptr(), c.data_ptr(), gp.data_ptr(), gl.data_ptr(),
+                                                              torch.cuda.current_stream(dev).cuda_stream))
+        return gp, gl, None, None, None, None, None, None, None, None
+
+
+def _robust_kl_hip_ok(pred, target, logstd, buf, weight, avg_factor, reduction):
+    if weight is not None or avg_factor is not None or reduction not in ('mean', 'sum'):
+        return False
+    if not (isinstance(pred, torch.Tensor) and isinstance(logstd, torch.Tensor)) or pred.device.type != 'cuda':
+        return False
+    if logstd.device != pred.device or logstd.shape != pred.shape or pred.numel() == 0:
+        return False
+    if buf.device != pred.device or buf.dtype != torch.float32 or buf.dim() != 0:
+        return False
+    if isinstance(target, int):
+        return target in (0, -1)
+    return isinstance(target, torch.Tensor) and target.device == pred.device and target.shape == pred.shape
+
+
+class RobustKLLoss(nn.Module):
+    """The reference's RobustKLLoss: same constructor, buffer ``mean_inv_std`` (0-dim fp32, initially 1, updated in training mode
+    only) and call forms.  CUDA inputs without ``weight`` / ``avg_factor`` and with reduction 'mean' or 'sum' run the HIP kernels;
+    everything else runs :func:`robust_kl_loss` in torch."""
+
+    def __init__(self, delta=1.414, reduction='mean', loss_weight=1.0, momentum=1.0, eps=1e-4):
+        super().__init__()
+        self.delta = delta
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+        self.eps = eps
+        self.momentum = momentum
+        self.register_buffer('mean_inv_std', torch.tensor(1, dtype=torch.float))
+
+    def forward(self, pred, target, logstd=None, weight=None, avg_factor=None, reduction_override=None, **kwargs):
+        if reduction_override not in (None, 'none', 'mean', 'sum'):
+            raise ValueError(f'RobustKLLoss: reduction_override {reduction_override!r}')
+        if kwargs:
+            raise TypeError(f'RobustKLLoss: unexpected arguments {sorted(kwargs)}')
+        reduction = reduction_override if reduction_override else self.reduction
+        if _robust_kl_hip_ok(pred, target, logstd, self.mean_inv_std, weight, avg_factor, reduction):
+            if isinstance(target, int):
+                x, mode = pred, target
+            else:
+                x, mode = pred - target, 0
+            loss = _RobustKLFunction.apply(x.to(torch.float32).contiguous(), logstd.to(torch.float32).contiguous(), self.mean_inv_std,
+                                           mode, float(self.delta), float(self.eps), float(self.momentum), self.training,
+                                           0 if reduction == 'mean' else 1, float(self.loss_weight))
+            return loss.to(pred.dtype)
+        loss = robust_kl_loss(pred, target, logstd=logstd, delta=self.delta, momentum=self.momentum, mean_inv_std=self.mean_inv_std,
+                              eps=self.eps, training=self.training)
+        return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+LOSSES = {'KLLossMV': KLLossMV, 'RobustKLLoss': RobustKLLoss}
 
 
 class UnbuiltLoss:
