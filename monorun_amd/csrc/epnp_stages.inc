@@ -15,20 +15,22 @@
 //              sequential loop replayed over the counts in RNG order, the winner's inlier mask / list, and the point sums of the
 //              re-fit (centroid, PCA, M^T M); an object whose loop goes on: the correspondences of its second round's samples
 //   refit_betas one quad per object: the re-fit's four eigenvectors, then lanes 0..2 = the beta candidates: the candidates' control
-//              points in the camera frame
-//   refit      one workgroup per object, one wave per candidate: the point sums (the waves' butterflies), pose and reprojection
-//              error of each, the best one's pose -> init_pose, init_ok, diag
+//              points in the camera frame, their pose (absolute orientation) and yaw
+//   refit      one workgroup per object, one wave per candidate: reprojection error of each over the inliers (the waves'
+//              butterflies), the best one's pose -> init_pose, init_ok, diag
 // The speculative hypotheses are solved in TWO ROUNDS: [0, first) for every object, [first, 30) only for the objects whose replayed loop
 // still wants iterations (the adaptive bound of RANSACUpdateNumIters drops to a handful after the first good model; the loop's state
 // parks in the workspace between the rounds).  Where the split falls changes the work, never the result.
 // Seven launches (round 3: thirteen); six for launch sets of fewer than 2048 objects, whose second round is ONE launch (epnp_round2_kernel).  Between the launches: a workspace laid out element-major ([element][problem]: a wave's accesses
-// to one element of consecutive problems are contiguous), 11.5 MB per 1024 objects since round 5 (round 4: 17 MB, round 3: 65 MB — the hypotheses' M^T M, control
+// to one element of consecutive problems are contiguous), 11.9 MB per 1024 objects since round 8 (round 5: 11.8 MB, round 4: 17 MB, round 3: 65 MB — the hypotheses' M^T M, control
 // points, coordinates and eigenvectors no longer leave the registers).
 
 constexpr int kEpMeta = 12;           // ints per object in the workspace
 constexpr int kEpSampRec = 28;        // floats per sample record (25 used; seven 16-byte loads)
 enum { EP_M_N = 0, EP_M_MODE, EP_M_NFIT, EP_M_REFIT, EP_M_ITERS, EP_M_BEST, EP_M_BESTH, EP_M_PENDING, EP_M_NITERS };
 enum { EP_MODE_FAIL = 0, EP_MODE_PLAIN = 1, EP_MODE_RANSAC = 2 };
+constexpr int kEpCandRec = 13;        // doubles per re-fit candidate record: R (9), t (3), yaw
+constexpr int kEpCandStride = 40;     // doubles per object of the records (three, one pad)
 
 struct EpnpWork {
     int *meta;            // [B][kEpMeta]: candidates, mode, points of the re-fit, re-fit wanted, iterations run, best count, best model,
@@ -42,7 +44,7 @@ struct EpnpWork {
     double *prep_r;       // [B][24]: control points (12), inverse of the control-point basis (9).  The per-object results below are object-major: one
                           //          workgroup (one XCD's L2) writes an object's values, and they share cache lines with no other object's
     double *mtm_r;        // [B][144]
-    double *ccs_r;        // [B][36]: the re-fit's three candidates' control points in the camera frame
+    double *cand_r;       // [B][kEpCandStride]: the re-fit's three candidate poses, kEpCandRec doubles each: R (row-major, 9), t (3), yaw = rvec[1]
     double *abt_r;        // [B][24]: the re-fit's absolute-orientation moments: sum a_j (4), sum a_j (pw - pw0) (4 x 3), sum (pw - pw0) (3), -, a(first inlier) (4)
     float *cam;           // [4][B]: fx fy cx cy of every object as the reference hands them to cv2 (float32), for the lane-mapped launches
     long long nq;
@@ -80,11 +82,11 @@ size_t epnp_work_bytes(int B, int P, EpnpWork *w, unsigned char *base) {
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_meta = take(sizeof(int) * kEpMeta * B), o_samp = take(sizeof(float) * kEpSampRec * nq), o_hrt = take(sizeof(double) * 12 * nq),
                  o_cand = take(sizeof(uint16_t) * ps * B), o_fit = take(sizeof(uint16_t) * ps * B), o_prep_r = take(sizeof(double) * 24 * B),
-                 o_mtm_r = take(sizeof(double) * 144 * B), o_ccs_r = take(sizeof(double) * 36 * B), o_cam = take(sizeof(float) * 4 * B), o_abt_r = take(sizeof(double) * 24 * B),
+                 o_mtm_r = take(sizeof(double) * 144 * B), o_cand_r = take(sizeof(double) * kEpCandStride * B), o_cam = take(sizeof(float) * 4 * B), o_abt_r = take(sizeof(double) * 24 * B),
                  o_spt = take(sizeof(uint16_t) * 5 * kEpMaxIters * B);
     if (w) {
         w->meta = (int *)(base + o_meta); w->samp = (float *)(base + o_samp); w->hrt = (double *)(base + o_hrt); w->cand = (uint16_t *)(base + o_cand);
-        w->fit = (uint16_t *)(base + o_fit); w->prep_r = (double *)(base + o_prep_r); w->mtm_r = (double *)(base + o_mtm_r); w->ccs_r = (double *)(base + o_ccs_r); w->cam = (float *)(base + o_cam); w->abt_r = (double *)(base + o_abt_r);
+        w->fit = (uint16_t *)(base + o_fit); w->prep_r = (double *)(base + o_prep_r); w->mtm_r = (double *)(base + o_mtm_r); w->cand_r = (double *)(base + o_cand_r); w->cam = (float *)(base + o_cam); w->abt_r = (double *)(base + o_abt_r);
         w->spt = (uint16_t *)(base + o_spt);
         w->nq = (long long)nq; w->pstride = (int)ps;
     }
@@ -1035,7 +1037,12 @@ __global__ void __launch_bounds__(256, MR_EP_QUAD_WAVES) epnp_round2_kernel(cons
 
 // ------------------------------------------------------------------------------------------------ the re-fit's eigenvectors and beta candidates
 // one QUAD per object: the four eigenvectors of the re-fit's M^T M (lane t: vector t), then lanes 0, 1, 2 = the candidates N = 1, 2, 3
-// (one code path): beta approximation, Gauss-Newton, the candidates' control points in the camera frame -> workspace
+// (one code path): beta approximation, Gauss-Newton, the candidates' control points in the camera frame, their absolute orientation and
+// yaw -> workspace (cand_r).  The pose needs only the consensus launch's moments, none of the tile: computed here, four lanes of a quad per
+// object, instead of in the prologue of the workgroup-per-object launch that evaluates the candidates (round 8).
+// With pc = sum_j a_j ccs_j the camera-frame centroid is pc0 = (sum_j S_j ccs_j) / n and the correlation sum (pc - pc0)(pw - pw0)^T is
+// sum_j ccs_j A_j^T - pc0 E^T (S_j = sum a_j, A_j = sum a_j (pw - pw0), E = sum (pw - pw0): ep_mtm_part); the first inlier must lie in
+// front of the camera, else the candidate's control points change sign.
 template <int LV>
 __global__ void __launch_bounds__(64, MR_EP_QUAD_WAVES) epnp_refit_betas_kernel(const EpnpStageArgs ea) {
     MR_EXACT
@@ -1067,16 +1074,50 @@ __global__ void __launch_bounds__(64, MR_EP_QUAD_WAVES) epnp_refit_betas_kernel(
     ep_betas_quad<LV>(sq, cand, be, wide, sqi);
     double ccs[4][3];
     ep_ccs_quad(z, be, ccs);
+    double R[9], t[3], rv[3];
+    {
+        const double *ab = ea.w.abt_r + b * 24;
+        double S[4], A[4][3], E[3], af[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { S[k] = ab[k]; af[k] = ab[20 + k]; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) A[k][c] = ab[4 + 3 * k + c];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) E[c] = ab[16 + c];
+        const double dn = (double)ea.w.meta[b * kEpMeta + EP_M_NFIT];          // = the inliers the LM launch lists from init_mask
+        const double zf = af[0] * ccs[0][2] + af[1] * ccs[1][2] + af[2] * ccs[2][2] + af[3] * ccs[3][2];
+        if (zf < 0.0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ccs[k][c] = -ccs[k][c];
+        }
+        double pc0[3], abt[9];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) pc0[r] = (S[0] * ccs[0][r] + S[1] * ccs[1][r] + S[2] * ccs[2][r] + S[3] * ccs[3][r]) / dn;
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                abt[3 * r + c] = fma(-pc0[r], E[c], fma(ccs[3][r], A[3][c], fma(ccs[2][r], A[2][c], fma(ccs[1][r], A[1][c], ccs[0][r] * A[0][c]))));
+        const double pw0[3] = { ea.w.prep_r[b * 24], ea.w.prep_r[b * 24 + 1], ea.w.prep_r[b * 24 + 2] };
+        ep_abt_to_pose(abt, pc0, pw0, R, t);
+        ep_rodrigues_to_vec(R, rv);
+    }
     if (j < 3 && sqi == 0) {
+        double *rec = ea.w.cand_r + b * kEpCandStride + kEpCandRec * cand;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 9; ++i) rec[i] = R[i];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) ea.w.ccs_r[(long long)b * 36 + (12 * cand + 3 * i + c)] = ccs[i][c];
+        for (int i = 0; i < 3; ++i) rec[9 + i] = t[i];
+        rec[12] = rv[1];
     }
 }
 
 // ------------------------------------------------------------------------------------------------ the re-fit's candidates, outputs
-constexpr int kEpRefitScratch = 3 * 14 + 6;         // doubles of LDS ep_refit_object works in: err | R | t of the three candidates, then pose and ok
+constexpr int kEpRefitScratch = 16;                 // doubles of LDS ep_refit_object works in: error | yaw | t of the three candidates (15, padded)
 size_t epnp_refit_lds_bytes(const PnpArgs &a) {
     size_t n = 0;
     n += sizeof(double) * kEpRefitScratch;
@@ -1097,12 +1138,53 @@ __device__ __forceinline__ void ep_store_init(uint8_t *init_ok, double *init_pos
     }
 }
 
-// The re-fit of ONE object by the waves of its workgroup (every wave of the workgroup calls this: three barriers inside): the three beta
-// candidates' absolute orientation (from the consensus launch's moments), reprojection error over the inliers `slist[0..nn)` of the tile `tl`; the best
-// candidate's pose (yaw, t) to every thread.  Shared by epnp_refit_kernel (three waves, geometry tile) and by the LM launch that carries
-// the re-fit as its prologue (pnp_uncert_refit_kernel: WPO waves, the LM's own tile) — candidate c is wave c mod NW's, every sum is one
-// wave's 64 interleaved partials + butterfly whichever wave that is, so both give the same bits.
-//   scand: [3][14] doubles of LDS (err, R, t of the candidates) + 6 (pose, ok).
+// The mean reprojection error over the inliers of the NC candidates c0, c0 + step, ... (< 3) of one wave, in ONE pass over the inliers:
+// each point is fetched once and feeds NC accumulators, each of them the per-lane sum the one-candidate pass forms (same terms, same
+// order), reduced by a wave_allreduce<1> of its own — the candidate's sum is one wave's 64 interleaved partials + butterfly whatever NC is.
+// Lane 0 leaves error, yaw and t of each candidate in scand[5 c ..].
+template <int NC, typename T, typename TL>
+__device__ __forceinline__ void ep_refit_errors(const EpRefitPoint<T, TL> &point, const EpCam &camu, const double *rec, const int c0, const int step,
+                                                const int nn, const double dn, const int lane, double *scand) {
+    MR_EXACT
+    double R[NC][9], t[NC][3], s[NC][1];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        const double *r = rec + kEpCandRec * (c0 + k * step);
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[k][i] = r[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) t[k][i] = r[9 + i];
+        s[k][0] = 0.0;
+    }
+    for (int i = lane; i < nn; i += 64) {
+        double pw[3], al[4], uu[2];
+        point(i, pw, al, uu);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+            const double Xc = ep_dot3(&R[k][0], pw) + t[k][0], Yc = ep_dot3(&R[k][3], pw) + t[k][1], iz = 1.0 / (ep_dot3(&R[k][6], pw) + t[k][2]);
+            const double du = uu[0] - (camu.cx + camu.fx * Xc * iz), dv = uu[1] - (camu.cy + camu.fy * Yc * iz);
+            s[k][0] += sqrt(du * du + dv * dv);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        wave_allreduce<1>(s[k]);
+        const int c = c0 + k * step;
+        if (lane == 0) {
+            scand[5 * c] = s[k][0] / dn; scand[5 * c + 1] = rec[kEpCandRec * c + 12];
+            scand[5 * c + 2] = t[k][0]; scand[5 * c + 3] = t[k][1]; scand[5 * c + 4] = t[k][2];
+        }
+    }
+}
+
+// The re-fit of ONE object by the waves of its workgroup (every wave of the workgroup calls this: one barrier inside): reprojection error
+// over the inliers `slist[0..nn)` of the tile `tl` of the three beta candidates whose poses refit_betas left in the workspace (cand_r);
+// the best candidate's pose (yaw, t) to every thread.  Shared by epnp_refit_kernel (three waves, geometry tile) and by the LM launch that
+// carries the re-fit as its prologue (pnp_uncert_refit_kernel: WPO waves, the LM's own tile) — candidate c is wave c mod NW's (a wave that
+// owns two or three evaluates them in one pass, ep_refit_errors), every sum is one wave's 64 interleaved partials + butterfly whichever wave
+// that is, so both give the same bits.  (Up to round 7 the candidates' absolute orientation and the best one's Rodrigues vector ran here, on
+// three lanes of wave 0 while the other waves waited at a barrier.)
+//   scand: [3][5] doubles of LDS (error, yaw, t of the candidates).
 template <typename T, int NW, typename TL>
 __device__ __forceinline__ bool ep_refit_object(const TL &tl, const uint16_t *slist, const int nn, double *scand, const EpCam &cam, const EpnpWork &w,
                                                 const long long B, const int b, const bool norm_f64, const int wid, const int lane, double (&pose)[4]) {
@@ -1116,84 +1198,22 @@ __device__ __forceinline__ bool ep_refit_object(const TL &tl, const uint16_t *sl
     EpCam camu;
     camu.fx = uni(cam.fx); camu.fy = uni(cam.fy); camu.cx = uni(cam.cx); camu.cy = uni(cam.cy);
     const EpRefitPoint<T, TL> point{ tl, slist, camu, cws, ci, uni(1.0 / cam.fx), uni(1.0 / cam.fy), norm_f64 };
-    // absolute orientation of the THREE candidates by three lanes of wave 0, from the moments the consensus launch left (ep_mtm_part): with
-    // pc = sum_j a_j ccs_j the camera-frame centroid is pc0 = (sum_j S_j ccs_j) / n and the correlation sum (pc - pc0)(pw - pw0)^T is
-    // sum_j ccs_j A_j^T - pc0 E^T  (S_j = sum a_j, A_j = sum a_j (pw - pw0), E = sum (pw - pw0)); the first inlier must lie in front of the
-    // camera, else the candidate's control points change sign.  (Round 5's earlier builds: two passes over the inliers per candidate.)
-    if (wid == 0) {
-        const int cnd = lane < 3 ? lane : 0;
-        double ccs[4][3], S[4], A[4][3], E[3], af[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ccs[j][k] = w.ccs_r[(long long)b * 36 + (12 * cnd + 3 * j + k)];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { S[j] = w.abt_r[(long long)b * 24 + j]; af[j] = w.abt_r[(long long)b * 24 + (20 + j)]; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) A[j][k] = w.abt_r[(long long)b * 24 + (4 + 3 * j + k)];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) E[k] = w.abt_r[(long long)b * 24 + (16 + k)];
-        const double zf = af[0] * ccs[0][2] + af[1] * ccs[1][2] + af[2] * ccs[2][2] + af[3] * ccs[3][2];
-        if (zf < 0.0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) ccs[j][k] = -ccs[j][k];
-        }
-        double pc0[3], abt[9], Rl[9], tl_[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) pc0[r] = (S[0] * ccs[0][r] + S[1] * ccs[1][r] + S[2] * ccs[2][r] + S[3] * ccs[3][r]) / dn;
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                abt[3 * r + k] = fma(-pc0[r], E[k], fma(ccs[3][r], A[3][k], fma(ccs[2][r], A[2][k], fma(ccs[1][r], A[1][k], ccs[0][r] * A[0][k]))));
-        const double pw0[3] = { cws[0][0], cws[0][1], cws[0][2] };
-        ep_abt_to_pose(abt, pc0, pw0, Rl, tl_);
-        if (lane < 3) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) scand[lane * 14 + 1 + i] = Rl[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) scand[lane * 14 + 10 + i] = tl_[i];
-        }
+    const double *rec = w.cand_r + (long long)b * kEpCandStride;
+    if constexpr (NW >= 3) {                              // one candidate per wave (waves 3.. idle)
+        if (wid < 3) ep_refit_errors<1, T>(point, camu, rec, wid, NW, nn, dn, lane, scand);
+    } else if constexpr (NW == 2) {                       // wave 0: candidates 0 and 2, wave 1: candidate 1
+        if (wid == 0) ep_refit_errors<2, T>(point, camu, rec, 0, 2, nn, dn, lane, scand);
+        else ep_refit_errors<1, T>(point, camu, rec, 1, 2, nn, dn, lane, scand);
+    } else {
+        ep_refit_errors<3, T>(point, camu, rec, 0, 1, nn, dn, lane, scand);
     }
     __syncthreads();
-    for (int cand = wid; cand < 3; cand += NW) {          // NW >= 3: one candidate per wave (waves 3.. idle): mean reprojection error over the inliers
-        double R[9], t[3];
+    int N = 0;
+    if (scand[5] < scand[0]) N = 1;
+    if (scand[10] < scand[N * 5]) N = 2;
 #pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = scand[cand * 14 + 1 + i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) t[i] = scand[cand * 14 + 10 + i];
-        double s1[1] = { 0.0 };
-        for (int i = lane; i < nn; i += 64) {
-            double pw[3], al[4], uu[2];
-            point(i, pw, al, uu);
-            const double Xc = ep_dot3(&R[0], pw) + t[0], Yc = ep_dot3(&R[3], pw) + t[1], iz = 1.0 / (ep_dot3(&R[6], pw) + t[2]);
-            const double du = uu[0] - (camu.cx + camu.fx * Xc * iz), dv = uu[1] - (camu.cy + camu.fy * Yc * iz);
-            s1[0] += sqrt(du * du + dv * dv);
-        }
-        wave_allreduce<1>(s1);
-        if (lane == 0) scand[cand * 14] = s1[0] / dn;                 // (R | t of the candidate are in scand already)
-    }
-    __syncthreads();
-    if (wid == 0) {                                       // the best candidate's Rodrigues vector
-        int N = 0;
-        if (scand[14] < scand[0]) N = 1;
-        if (scand[28] < scand[N * 14]) N = 2;
-        double R[9], rv[3];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = scand[N * 14 + 1 + i];
-        ep_rodrigues_to_vec(R, rv);
-        const double p0 = rv[1], p1 = scand[N * 14 + 10], p2 = scand[N * 14 + 11], p3 = scand[N * 14 + 12];
-        const bool fin = isfinite(p0) && isfinite(p1) && isfinite(p2) && isfinite(p3);
-        if (lane == 0) { scand[42] = p0; scand[43] = p1; scand[44] = p2; scand[45] = p3; scand[46] = fin ? 1.0 : 0.0; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) pose[j] = scand[42 + j];
-    return scand[46] != 0.0;
+    for (int j = 0; j < 4; ++j) pose[j] = scand[N * 5 + 1 + j];
+    return isfinite(pose[0]) && isfinite(pose[1]) && isfinite(pose[2]) && isfinite(pose[3]);
 }
 
 template <typename T>
@@ -1211,7 +1231,7 @@ __global__ void __launch_bounds__(kEpPoseThreads, MR_EP_REFIT_WAVES) epnp_refit_
     double pose[4] = { 0.0, 0.0, 0.0, 0.0 };
     if (ok) {                                             // block-uniform
         extern __shared__ __align__(16) unsigned char smem[];
-        double *scand = (double *)smem;                                          // [3][14] + 6
+        double *scand = (double *)smem;                                          // [3][5]
         unsigned char *tile_base = (unsigned char *)(scand + kEpRefitScratch);
         Tile<T> tl;
         tl.ra = (const T *)tile_base; tl.rb = (const T *)tile_base + (size_t)4 * P;
