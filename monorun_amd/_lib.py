@@ -6,6 +6,7 @@ The library is built in-tree by hipcc for gfx950 (``build()``; also driven by
 There is NO CPU fallback: if the library is missing or no HIP device is present the ops raise.
 """
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -35,7 +36,8 @@ def _stale():
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    deps = [SRC, os.path.join(_HERE, "csrc", "pnp_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_kernel_body.inc"), os.path.join(_HERE, "csrc", "pnp6_kernel.inc"), os.path.join(_HERE, "csrc", "hessian_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_backward_kernel.inc"), os.path.join(_HERE, "csrc", "pnp_noc_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_kernel.inc"), os.path.join(_HERE, "csrc", "epnp_eig_low4.inc"), os.path.join(_HERE, "csrc", "epnp_stages.inc"), os.path.join(_HERE, "csrc", "epnp_consensus_body.inc"), os.path.join(_HERE, "csrc", "kitti_eval_kernel.inc"), os.path.join(_HERE, "csrc", "iou3d_kernel.inc"), os.path.join(_HERE, "csrc", "projection_loss_kernel.inc"), os.path.join(INCLUDE, "monorun_pnp.h")]
+    csrc = os.path.join(_HERE, 'csrc')
+    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [os.path.join(INCLUDE, 'monorun_pnp.h')]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 

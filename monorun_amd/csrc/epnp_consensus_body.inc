@@ -56,9 +56,6 @@
         for (int i = tid; i < 4 * 32; i += NT) scnt[i] = 0;
         for (int i = tid; i < (P + 31) >> 5; i += NT) smask[i] = 0u;
         __syncthreads();
-#if defined(EP_CONS_EXIT) && EP_CONS_EXIT == 1
-        return;
-#endif
 
         // ---- consensus of every hypothesis over the candidates
         const float thr2 = (float)((double)thr_given * (double)thr_given);
@@ -86,9 +83,6 @@
             }
         }
         __syncthreads();
-#if defined(EP_CONS_EXIT) && EP_CONS_EXIT == 2
-        return;
-#endif
 
         // ---- RANSAC's loop replayed over the counts, in RNG order (ptsetreg.cpp run), as far as this round's hypotheses reach
         // (by wave 0 alone, its state through LDS: RANSACUpdateNumIters is a pow and two logs of the device math library — ~600
@@ -156,9 +150,6 @@
             for (int p = tid; p < P; p += NT) cv.init_mask[(long long)b * P + p] = (uint8_t)((smask[p >> 5] >> (p & 31)) & 1u);
         }
     } else __syncthreads();
-#if defined(EP_CONS_EXIT) && EP_CONS_EXIT == 3
-        return;
-#endif
 
     if (ok) {
         // ---- EPnP on the whole set (the re-fit on the inliers, or plain solvePnP): A) centroid, covariance -> control points,
@@ -204,9 +195,6 @@
             }
         }
         __syncthreads();
-#if defined(EP_CONS_EXIT) && EP_CONS_EXIT == 4
-        return;
-#endif
 
         // what every point needs of the above is wave-uniform: into scalar registers (the accumulators below want the vector ones)
         double cws[4][3], ci[9];
@@ -222,12 +210,8 @@
         const double pw0[3] = { cws[0][0], cws[0][1], cws[0][2] };
 #define EP_MTM_DO(W_) do { ep_mtm_part<W_, T>(point, camu, pw0, nn, lane, acc, ext, afirst); \
                           if (lane == 0) { ep_mtm_store<W_>(acc, camu, ea.w.mtm_r, B, b); ep_abt_store<W_>(ext, afirst, ea.w.abt_r, B, b); } } while (0)
-        if constexpr (WPO == 4) {
-            if (wid == 0) EP_MTM_DO(0); else if (wid == 1) EP_MTM_DO(1); else if (wid == 2) EP_MTM_DO(2); else EP_MTM_DO(3);
-        } else {                                          // two waves: parts 0, 2 and 1, 3 (each part's sums are its own: same values)
-            static_assert(WPO == 2, "");
-            if (wid == 0) { EP_MTM_DO(0); EP_MTM_DO(2); } else { EP_MTM_DO(1); EP_MTM_DO(3); }
-        }
+        static_assert(WPO == 4, "one M^T M part per wave");
+        if (wid == 0) EP_MTM_DO(0); else if (wid == 1) EP_MTM_DO(1); else if (wid == 2) EP_MTM_DO(2); else EP_MTM_DO(3);
 #undef EP_MTM_DO
         for (int i = tid; i < nn; i += NT) ea.w.fit[(long long)b * ea.w.pstride + i] = list[i];
     }

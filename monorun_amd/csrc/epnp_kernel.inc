@@ -3,7 +3,7 @@
 //     cv2.solvePnP(X, x, K, 0, flags=SOLVEPNP_EPNP)          (/root/reference/monorun/ops/least_squares/pnp_uncert_cpu.py:33-68)
 // for a batch of objects, feeding (init_pose, inlier mask) to the LM launch.  This file: the scalar building blocks (small dense
 // linear algebra in registers, beta approximations, Gauss-Newton, absolute orientation, Rodrigues, the istd candidate stage, the
-// RANSAC bookkeeping); epnp_eig_lanes.inc: the 12x12 eigen-solver; epnp_stages.inc: the launches.
+// RANSAC bookkeeping); epnp_eig_low4.inc: the 12x12 eigen-solver; epnp_stages.inc: the launches.
 //
 // OpenCV is third-party and absent; the arithmetic followed here is the published algorithm as the test infrastructure specifies
 // it operation for operation (EPnP: control points by PCA, barycentric coordinates, M^T M, its four smallest eigenvectors, three

@@ -796,26 +796,17 @@ __device__ __forceinline__ void ep_hyp_body(const EpnpStageArgs &ea, const int b
             }
         }
         }
-#if EP_HYP_CUT == 1
-        { double *o = ea.w.hrt + q; for (int s = 0; s < 3; ++s) for (int c = 0; c < 12; ++c) o[(12 * s + c) * nq] = a[s][c]; return; }
-#endif
         double lam;
         EP_STAMP(3);
         ep_eig12_low4_quad<LV>(a, z, lam, sq.p + kQL * 16, EP_EIG_STAMPS, sqi);
         EP_STAMP(4);
     }
-#if EP_HYP_CUT == 2
-        { double *o = ea.w.hrt + q; for (int c = 0; c < 12; ++c) o[c * nq] = z[c]; return; }
-#endif
     const int cand = j == 3 ? 0 : j;
     double be[4];
     ep_L_rho_quad<LV>(z, sq, wide, sqi);
     EP_STAMP(5);
     ep_betas_quad<LV>(sq, cand, be, wide, sqi);
     EP_STAMP(7);
-#if EP_HYP_CUT == 3
-        { double *o = ea.w.hrt + q; for (int c = 0; c < 12; ++c) o[c * nq] = z[c] + be[c & 3]; return; }
-#endif
     double R[9], t[3], err;
     {
         double ccs[4][3];
@@ -828,9 +819,6 @@ __device__ __forceinline__ void ep_hyp_body(const EpnpStageArgs &ea, const int b
         ep_pose5_quad(k, ccs, sq, pws, us, R, t, err);
     }
     EP_STAMP(8);
-#if EP_HYP_CUT == 4
-        { double *o = ea.w.hrt + q; for (int c = 0; c < 12; ++c) o[c * nq] = c < 9 ? R[c] : t[c - 9] + err; return; }
-#endif
     // the Rodrigues round trip of solvePnP's output (rvec out, Rodrigues(rvec) in the RANSAC callback), every candidate lane its own
     double R2[9];
     {
@@ -993,8 +981,7 @@ __device__ __forceinline__ void ep_mtm_store(const double (&acc)[12], const EpCa
     }
 }
 
-// WPO = waves per object: 4 is what the library launches; 2 exists for the experiment that rejected it (same sums, same bits; fewer wave slots
-// per object for longer: slower in every regime, monorun_pnp.hip launch_epnp_stages).
+// WPO = waves per object: 4, the one instantiation (two measured slower in every regime: profiles/r05_epnp_grouping.txt)
 template <typename T, int WPO>
 __global__ void __launch_bounds__(64 * WPO, MR_EP_CONS_WAVES) epnp_consensus_kernel(const EpnpStageArgs ea) {
     extern __shared__ __align__(16) unsigned char smem[];

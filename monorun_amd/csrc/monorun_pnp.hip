@@ -399,7 +399,7 @@ __device__ __forceinline__ void decode_pixel_pair(const DecodeArgs &a, const Dec
 // K2, vector form: one thread per FOUR consecutive RoI pixels of one object — five 16-byte loads of the selected head channels,
 // seven 16-byte NON-TEMPORAL stores of the decoded channels.  One workgroup per object (grid = B).  Same per-pixel arithmetic as the
 // scalar kernel above (two pixels per packed instruction), hence bit-identical outputs.  What bounds it, as measured (per-wave 100 MHz
-// stamps of a -DMR_K2_EXPERIMENT build, tools/gpu_k2_timeline.py, profiles/r04_k2_timeline.txt, r04_k2_store_policy.txt):
+// stamps, profiles/r04_k2_timeline.txt, r04_k2_store_policy.txt):
 //   * a wave has its parameters 2.0 us after it starts (three dependent rounds of loads), its pixel loads out 0.9 us later, the data
 //     0.5 us later — the pixel data is NOT what is late —, its arithmetic done after another 3.1 us; waves start within 0.7 us;
 //   * with plain stores the profiler counted 2 - 3 us more than the last wave's end: the write-back of the 22 MB of outputs from L2 when
@@ -413,17 +413,7 @@ __device__ __forceinline__ void decode_pixel_pair(const DecodeArgs &a, const Dec
 // chains interleaved across four pixels.  Requires fp32 head output, h * w % 4 == 0 and < 65536, no coord_2d map (the launcher falls
 // back to the scalar kernel otherwise).
 template <int THREADS, int TRIPS>
-__global__ void __launch_bounds__(THREADS) noc_decode_kernel_x4(const DecodeArgs a, int quads_per_obj
-#ifdef MR_K2_EXPERIMENT
-    , unsigned long long *stamps
-#endif
-    ) {
-#ifdef MR_K2_EXPERIMENT
-#define K2_STAMP(i) do { if (stamps && (threadIdx.x & 63) == 0) stamps[((long long)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6)) * 8 + (i)] = wall_clock64(); } while (0)
-    K2_STAMP(0);
-#else
-#define K2_STAMP(i) do { } while (0)
-#endif
+__global__ void __launch_bounds__(THREADS) noc_decode_kernel_x4(const DecodeArgs a, int quads_per_obj) {
     // one workgroup per object: the object index is wave-uniform, so its parameters (label, flip, dims, RoI, coder constants — two
     // dependent rounds of loads) are fetched through the scalar cache once per wave instead of once per lane.  A thread takes up
     // to TRIPS pixel quads (q = t, t + THREADS, ...): all their loads are issued before the first quad is decoded, so the
@@ -444,7 +434,6 @@ __global__ void __launch_bounds__(THREADS) noc_decode_kernel_x4(const DecodeArgs
     }
     const float *ap = (const float *)a.all_pred;
     const double rc_sd_sq = 1.0 / (double)a.sd_sq, rc_std_scale = 1.0 / (double)a.std_scale;      // div_by_uniform
-    K2_STAMP(1);
     if constexpr (TRIPS == 1) {
         // The last wave of an object owns only the quads left over (28x28: 4 of 196) and would still issue the whole two-pairs-per-lane
         // instruction stream for them.  With at most 32 quads left it works on PAIRS instead: lane l takes pixels (2l, 2l + 1) of the
@@ -488,10 +477,6 @@ __global__ void __launch_bounds__(THREADS) noc_decode_kernel_x4(const DecodeArgs
                 for (int k = 0; k < 2; ++k) in[t][3 + k] = *(const float4 *)(ap + o.base + (long long)(o.ch_ls + k) * hw + 4 * q);
             }
         }
-#ifdef MR_K2_EXPERIMENT
-        K2_STAMP(2);
-        if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); K2_STAMP(3); }
-#endif
 #pragma unroll
         for (int t = 0; t < TRIPS; ++t) {
             const int q = q0 + t * THREADS;
@@ -509,11 +494,7 @@ __global__ void __launch_bounds__(THREADS) noc_decode_kernel_x4(const DecodeArgs
                     for (int k = 0; k < 3; ++k) { noc[k].x = ((const float *)&in[t][k])[j]; noc[k].y = ((const float *)&in[t][k])[j + 1]; }
 #pragma unroll
                     for (int k = 0; k < 2; ++k) { ls[k].x = ((const float *)&in[t][3 + k])[j]; ls[k].y = ((const float *)&in[t][3 + k])[j + 1]; }
-#ifdef MR_K2_COPY_ONLY      // ubench: the kernel's memory traffic without its arithmetic (tools/profile_k2_quick.sh on a variant build)
-                    c2[0] = noc[0]; c2[1] = noc[1]; w2[0] = ls[0]; w2[1] = ls[1]; c3[0] = noc[2]; c3[1] = noc[0] + ls[0]; c3[2] = noc[1] + ls[1];
-#else
                     decode_pixel_pair<CHECKED>(a, o, p0 + j, noc, ls, c2, w2, c3, rc_sd_sq, rc_std_scale, w_magic, special);
-#endif
                     out[0][j] = c2[0].x; out[0][j + 1] = c2[0].y; out[1][j] = c2[1].x; out[1][j + 1] = c2[1].y;
                     out[2][j] = w2[0].x; out[2][j + 1] = w2[0].y; out[3][j] = w2[1].x; out[3][j + 1] = w2[1].y;
 #pragma unroll
@@ -533,16 +514,10 @@ __global__ void __launch_bounds__(THREADS) noc_decode_kernel_x4(const DecodeArgs
                 st4(a.c2d + ((long long)b * 2 + k) * hw + p0, out[k]);
                 st4(a.istd + ((long long)b * 2 + k) * hw + p0, out[2 + k]);
             }
-            K2_STAMP(4);
 #pragma unroll
             for (int k = 0; k < 3; ++k) st4(a.c3d + ((long long)b * 3 + k) * hw + p0, out[4 + k]);
         }
     }
-#ifdef MR_K2_EXPERIMENT
-    K2_STAMP(5);
-    if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); K2_STAMP(6); }
-#endif
-#undef K2_STAMP
 }
 
 // numpy's pairwise summation tree for a length-P contiguous float32 reduction, built on the host:
@@ -857,90 +832,79 @@ DevInfo dev_info() {
 }
 constexpr int kSimdsPerCu = 4;
 
-template <typename T, int WPO>
-int launch(const PnpArgs &a, hipStream_t st) {
+// Opts a kernel in to more dynamic LDS than the default 48 KB.  The grant is a per-device function attribute, kept per (kernel, device):
+// raised monotonically and under a lock (two host threads with different sizes must not shrink it between the other's set and launch),
+// and no driver call in the steady state.  Launches within the default take neither the lock nor the attribute.
+int grant_lds(const void *fn, size_t lds) {
+    if (lds <= 48 * 1024) return MR_OK;
+    static std::mutex mu; static std::map<std::pair<const void *, int>, size_t> granted;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    size_t &g = granted[std::make_pair(fn, dev)];
+    if (lds > g) {
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        g = lds;
+    }
+    return MR_OK;
+}
+
+// One launch of an LM kernel: a workgroup of WPO waves per object, the LDS lds_bytes() carves, `a` and then `more` as the kernel's arguments.
+// any_order (MR_ANY_ORDER, for the kernels that honour it): no barrier bit on the dispatch packet — the launch starts once the launch in front of
+// it has STARTED (the LM launches of the calls of one launch set: the first waits for the set's initialiser launches, the others run beside it —
+// PnPEpnpGroupLaunch).
+template <int WPO, typename Kernel, typename... More>
+int launch_lm(Kernel kernel, bool any_order, const PnpArgs &a, hipStream_t st, const More &... more) {
     const size_t lds = lds_bytes(a, WPO);
     if (lds > dev_info().lds_per_cu) return MR_ERR_UNSUPPORTED;
-    if (lds > 48 * 1024) {
-        // the opt-in is a per-device function attribute: remember what was granted on each device
-        static std::mutex mu; static size_t granted[kMaxDevices] = {};
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= kMaxDevices || lds > granted[dev]) {
-            HIP_TRY(hipFuncSetAttribute((const void *)pnp_uncert_kernel<T, WPO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev >= 0 && dev < kMaxDevices) granted[dev] = lds;
-        }
-    }
-    if (a.flags & MR_ANY_ORDER)      // no barrier bit on the dispatch packet: the launch need not wait for earlier launches on this stream
-        hipExtLaunchKernelGGL((pnp_uncert_kernel<T, WPO>), dim3(a.B), dim3(64 * WPO), (uint32_t)lds, st, nullptr, nullptr, hipExtAnyOrderLaunch, a);
-    else
-        hipLaunchKernelGGL((pnp_uncert_kernel<T, WPO>), dim3(a.B), dim3(64 * WPO), lds, st, a);
+    int r;
+    if ((r = grant_lds((const void *)kernel, lds)) != MR_OK) return r;
+    if (any_order) hipExtLaunchKernelGGL(kernel, dim3(a.B), dim3(64 * WPO), (uint32_t)lds, st, nullptr, nullptr, hipExtAnyOrderLaunch, a, more...);
+    else hipLaunchKernelGGL(kernel, dim3(a.B), dim3(64 * WPO), lds, st, a, more...);
     HIP_TRY(hipGetLastError());
     return MR_OK;
 }
 
-int grant_lds(const void *fn, size_t lds);
-
+// the fast mode's launch: the object's own initialiser (K0) inside the kernel
 template <typename T, int WPO>
-int launch_ext(const PnpArgs &a, hipStream_t st, const PnpCallTable *tbl = nullptr, const EpnpRefitIn *rf = nullptr) {
-    const size_t lds = lds_bytes(a, WPO);
-    if (lds > dev_info().lds_per_cu) return MR_ERR_UNSUPPORTED;
-    if (rf) {                               // the initialiser's re-fit as this launch's prologue (mr_pnp_uncert_from_epnp_grouped)
-        if (!tbl) return MR_ERR_BAD_ARGUMENT;
-        int r;
-        if (lds > 48 * 1024 && (r = grant_lds((const void *)pnp_uncert_refit_kernel<T, WPO>, lds)) != MR_OK) return r;
-        hipLaunchKernelGGL((pnp_uncert_refit_kernel<T, WPO>), dim3(a.B), dim3(64 * WPO), lds, st, a, *tbl, *rf);
-        HIP_TRY(hipGetLastError());
-        return MR_OK;
-    }
-    if (tbl) {                              // the objects of several calls: the kernel that takes the call table as a second argument
-        if (lds > 48 * 1024) {
-            static std::mutex mu; static size_t granted[kMaxDevices] = {};
-            int dev = 0;
-            HIP_TRY(hipGetDevice(&dev));
-            std::lock_guard<std::mutex> lk(mu);
-            if (dev < 0 || dev >= kMaxDevices || lds > granted[dev]) {
-                HIP_TRY(hipFuncSetAttribute((const void *)pnp_uncert_group_kernel<T, WPO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                if (dev >= 0 && dev < kMaxDevices) granted[dev] = lds;
-            }
-        }
-        hipLaunchKernelGGL((pnp_uncert_group_kernel<T, WPO>), dim3(a.B), dim3(64 * WPO), lds, st, a, *tbl);
-        HIP_TRY(hipGetLastError());
-        return MR_OK;
-    }
-    if (lds > 48 * 1024) {
-        static std::mutex mu; static size_t granted[kMaxDevices] = {};
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= kMaxDevices || lds > granted[dev]) {
-            HIP_TRY(hipFuncSetAttribute((const void *)pnp_uncert_kernel<T, WPO, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev >= 0 && dev < kMaxDevices) granted[dev] = lds;
-        }
-    }
-    if (a.flags & MR_ANY_ORDER)      // no barrier bit on the dispatch packet: the launch starts once the launch in front of it has STARTED (the LM launches
-        // of the calls of one launch set: the first waits for the set's initialiser launches, the others run beside it — PnPEpnpGroupLaunch)
-        hipExtLaunchKernelGGL((pnp_uncert_kernel<T, WPO, true>), dim3(a.B), dim3(64 * WPO), (uint32_t)lds, st, nullptr, nullptr, hipExtAnyOrderLaunch, a);
-    else
-        hipLaunchKernelGGL((pnp_uncert_kernel<T, WPO, true>), dim3(a.B), dim3(64 * WPO), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return MR_OK;
+int launch(const PnpArgs &a, hipStream_t st) { return launch_lm<WPO>(pnp_uncert_kernel<T, WPO>, a.flags & MR_ANY_ORDER, a, st); }
+
+// behind an external initialiser: with the initialiser's re-fit as the launch's prologue (rf: mr_pnp_uncert_from_epnp_grouped; always with a
+// call table), over the objects of several calls (tbl: the kernel that takes the call table as a second argument), or over one call's objects
+template <typename T, int WPO>
+int launch_ext(const PnpArgs &a, hipStream_t st, const PnpCallTable *tbl, const EpnpRefitIn *rf) {
+    if (rf) return launch_lm<WPO>(pnp_uncert_refit_kernel<T, WPO>, false, a, st, *tbl, *rf);
+    if (tbl) return launch_lm<WPO>(pnp_uncert_group_kernel<T, WPO>, false, a, st, *tbl);
+    return launch_lm<WPO>(pnp_uncert_kernel<T, WPO, true>, a.flags & MR_ANY_ORDER, a, st);
 }
 
 // the instantiations of the external-initialiser launch (launch_ext): 2, 4 or 8 waves per object
 int ext_wpo(int wpo) { return wpo < 2 ? 2 : (wpo == 3 ? 4 : wpo); }
 
+// What a launch derives from its arguments: the storage size, the coalesced per-point loads (channel-planar rows: point stride 1 on all three
+// tensors; never from_head, whose tile is decoded in-kernel) and, for PnpArgs, the LDS carve: chunk slots (multiple of 4), pairwise leaves (>= 1).
+template <typename T, class A>
+void derive_launch_fields(A &a) {
+    a.elem_size = (int)sizeof(T);
+    a.vec = (!a.from_head && a.s2[1] == 1 && a.sw[1] == 1 && a.s3[1] == 1) ? 1 : 0;
+    if constexpr (std::is_same<A, PnpArgs>::value) {
+        a.nca = (((a.P + 63) / 64) + 3) & ~3;
+        a.nla = a.plan.n_leaves > 0 ? a.plan.n_leaves : 1;
+    }
+}
+
+// Ceres' max_num_iterations: 50 unless the MR_LM_MAXIT bits of `flags` are set
+int lm_max_iter(int flags) {
+    const int mi = (flags & MR_LM_MAXIT_MASK) >> MR_LM_MAXIT_SHIFT;
+    return mi ? mi : 50;
+}
+
 template <typename T>
 int launch_wpo(PnpArgs &a, int wpo, hipStream_t st, const PnpCallTable *tbl = nullptr, const EpnpRefitIn *rf = nullptr) {
-    a.elem_size = (int)sizeof(T);
-    a.vec = (!a.from_head && a.s2[1] == 1 && a.sw[1] == 1 && a.s3[1] == 1) ? 1 : 0;      // channel-planar rows: coalesced per-point loads
-    a.nca = (((a.P + 63) / 64) + 3) & ~3;
-    a.nla = a.plan.n_leaves > 0 ? a.plan.n_leaves : 1;
-    { const int mi = (a.flags & MR_LM_MAXIT_MASK) >> MR_LM_MAXIT_SHIFT; a.lm_max_iter = mi ? mi : 50; }
+    derive_launch_fields<T>(a);
+    a.lm_max_iter = lm_max_iter(a.flags);
     if (a.init_mask) {                      // external initialiser: 2, 4 or 8 waves per object
-        wpo = ext_wpo(wpo);
-        switch (wpo) {
+        switch (ext_wpo(wpo)) {
             case 2: return launch_ext<T, 2>(a, st, tbl, rf);
             case 4: return launch_ext<T, 4>(a, st, tbl, rf);
             case 8: return launch_ext<T, 8>(a, st, tbl, rf);
@@ -1009,40 +973,15 @@ __global__ void __launch_bounds__(64 * WPO) block_sum_probe_kernel(const double 
 // 6-DoF refinement (second launch of pnp_uncert(..., use_6dof=True)): see pnp6_kernel.inc
 template <typename T>
 int launch_pnp6(Pnp6Args &a, hipStream_t st) {
-    a.elem_size = (int)sizeof(T);
-    a.vec = (a.s2[1] == 1 && a.sw[1] == 1 && a.s3[1] == 1) ? 1 : 0;
+    derive_launch_fields<T>(a);
     const int nchunk = (a.P + 63) / 64;
     const size_t lds = sizeof(double) * 2 * 4 * kRedN + sizeof(unsigned long long) * ((nchunk + 3) & ~3) + (size_t)8 * a.P * sizeof(T) +
                        sizeof(uint16_t) * ((a.P + 7) & ~7) + 16;
     if (lds > dev_info().lds_per_cu) return MR_ERR_UNSUPPORTED;
-    if (lds > 48 * 1024) {
-        // per-device function attribute, raised monotonically under a lock (two host threads with different P must not shrink it
-        // between the other's set and launch), and no driver call in the steady state — the pattern of launch<T, WPO>
-        static std::mutex mu; static size_t granted[kMaxDevices] = {};
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev < 0 || dev >= kMaxDevices || lds > granted[dev]) {
-            HIP_TRY(hipFuncSetAttribute((const void *)pnp6_refine_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if (dev >= 0 && dev < kMaxDevices) granted[dev] = lds;
-        }
-    }
+    int r;
+    if ((r = grant_lds((const void *)pnp6_refine_kernel<T>, lds)) != MR_OK) return r;
     hipLaunchKernelGGL((pnp6_refine_kernel<T>), dim3(a.B), dim3(kThreads6), lds, st, a);
     HIP_TRY(hipGetLastError());
-    return MR_OK;
-}
-
-// opt-in to more than 64 KB of dynamic LDS, once per (kernel, device, size)
-int grant_lds(const void *fn, size_t lds) {
-    static std::mutex mu; static std::map<std::pair<const void *, int>, size_t> granted;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(mu);
-    size_t &g = granted[std::make_pair(fn, dev)];
-    if (lds > g) {
-        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        g = lds;
-    }
     return MR_OK;
 }
 
@@ -1051,17 +990,8 @@ int grant_lds(const void *fn, size_t lds) {
 template <typename T>
 int launch_epnp_stages(EpnpStageArgs &ea, void *workspace, size_t workspace_bytes, int first_round, hipStream_t st) {
     PnpArgs &a = ea.p;
-    a.elem_size = (int)sizeof(T);
-    a.vec = (a.s2[1] == 1 && a.sw[1] == 1 && a.s3[1] == 1) ? 1 : 0;
-    a.nca = (((a.P + 63) / 64) + 3) & ~3;
-    a.nla = a.plan.n_leaves > 0 ? a.plan.n_leaves : 1;
-#ifndef MR_EP_LDS_PAD_CONS
-#define MR_EP_LDS_PAD_CONS 0      // development aid: extra LDS per workgroup of the consensus / re-fit launch (residency experiments)
-#endif
-#ifndef MR_EP_LDS_PAD_REFIT
-#define MR_EP_LDS_PAD_REFIT 0
-#endif
-    const size_t lds_f = epnp_front_lds_bytes(a), lds_c = epnp_consensus_lds_bytes(a) + MR_EP_LDS_PAD_CONS, lds_r = epnp_refit_lds_bytes(a) + MR_EP_LDS_PAD_REFIT;
+    derive_launch_fields<T>(a);
+    const size_t lds_f = epnp_front_lds_bytes(a), lds_c = epnp_consensus_lds_bytes(a), lds_r = epnp_refit_lds_bytes(a);
     if (lds_f > dev_info().lds_per_cu || lds_c > dev_info().lds_per_cu || lds_r > dev_info().lds_per_cu) return MR_ERR_UNSUPPORTED;
     const size_t need = epnp_work_bytes(a.B, a.P, nullptr, nullptr);
     unsigned char *base = (unsigned char *)workspace;
@@ -1098,12 +1028,7 @@ int launch_epnp_stages(EpnpStageArgs &ea, void *workspace, size_t workspace_byte
     auto run = [&]() -> int {
         int r;
         if ((r = grant_lds((const void *)epnp_front_kernel<T>, lds_f)) != MR_OK) return r;
-        // waves per object of the consensus launch: 4; the environment variable MR_EP_CONS_WPO=2 selects the two-wave instantiation (same bits; measured
-        // slower one call at a time AND in launch sets — 11.39 -> 11.21 M solves/s with sets of five, 11.93 -> 11.51 with sets of eight: the launch's
-        // time is throughput work, not waves waiting — profiles/r05_epnp_grouping.txt)
-        static const int cons_env = [] { const char *e = getenv("MR_EP_CONS_WPO"); const int v = e ? atoi(e) : 0; return (v == 2 || v == 4) ? v : 0; }();
-        const int cons_wpo = cons_env ? cons_env : 4;
-        if ((r = grant_lds(cons_wpo == 2 ? (const void *)epnp_consensus_kernel<T, 2> : (const void *)epnp_consensus_kernel<T, 4>, lds_c)) != MR_OK) return r;
+        if ((r = grant_lds((const void *)epnp_consensus_kernel<T, 4>, lds_c)) != MR_OK) return r;
         if ((r = grant_lds((const void *)epnp_refit_kernel<T>, lds_r)) != MR_OK) return r;
         // The 30 hypotheses of an object are solved in two rounds: [0, first) for every object, the rest only for the objects whose
         // replayed loop still wants iterations after `first` (ptsetreg.cpp's adaptive bound: with few outliers it drops to a
@@ -1117,13 +1042,13 @@ int launch_epnp_stages(EpnpStageArgs &ea, void *workspace, size_t workspace_byte
         static const int wide_env = lv_env("MR_EP_WIDE");
         static const int wide_hyp_env = lv_env("MR_EP_WIDE_HYP") >= 0 ? lv_env("MR_EP_WIDE_HYP") : wide_env, wide_betas_env = lv_env("MR_EP_WIDE_BETAS") >= 0 ? lv_env("MR_EP_WIDE_BETAS") : wide_env;
         static const int r2_env = [] { const char *e = getenv("MR_EP_ROUND2"); return e ? atoi(e) : 0; }();      // development: 1 = always two launches, 2 = always one
-        const bool one_launch_round2 = cons_wpo == 4 && (kEpMaxIters - first) <= kEpRound2Quads && first < kEpMaxIters && (r2_env == 2 || (r2_env == 0 && a.B < 2048));
+        const bool one_launch_round2 = (kEpMaxIters - first) <= kEpRound2Quads && first < kEpMaxIters && (r2_env == 2 || (r2_env == 0 && a.B < 2048));
         for (int round = 0; round < 2; ++round) {
             ea.h0 = round == 0 ? 0 : first; ea.h1 = round == 0 ? first : kEpMaxIters;
             const int nh = ea.h1 - ea.h0;
             if (nh <= 0) break;
             if (round == 1 && one_launch_round2) {
-                const size_t lds_2 = epnp_round2_lds_bytes(a) + MR_EP_LDS_PAD_CONS;
+                const size_t lds_2 = epnp_round2_lds_bytes(a);
                 if ((r = grant_lds((const void *)epnp_round2_kernel<T>, lds_2)) != MR_OK) return r;
                 hipLaunchKernelGGL((epnp_round2_kernel<T>), dim3(a.B), dim3(256), lds_2, st, ea);
                 break;
@@ -1138,8 +1063,7 @@ int launch_epnp_stages(EpnpStageArgs &ea, void *workspace, size_t workspace_byte
             if (lv_h == 4) hipLaunchKernelGGL(epnp_hyp_kernel<4>, dim3((unsigned)quads), dim3(64), 0, st, ea);
             else if (lv_h == 2) hipLaunchKernelGGL(epnp_hyp_kernel<2>, dim3((unsigned)((quads + 3) / 4)), dim3(64), 0, st, ea);
             else hipLaunchKernelGGL(epnp_hyp_kernel<0>, dim3((unsigned)((quads + 15) / 16)), dim3(64), 0, st, ea);
-            if (cons_wpo == 2) hipLaunchKernelGGL((epnp_consensus_kernel<T, 2>), dim3(a.B), dim3(128), lds_c, st, ea);
-            else hipLaunchKernelGGL((epnp_consensus_kernel<T, 4>), dim3(a.B), dim3(256), lds_c, st, ea);
+            hipLaunchKernelGGL((epnp_consensus_kernel<T, 4>), dim3(a.B), dim3(256), lds_c, st, ea);      // 4 waves per object (epnp_stages.inc)
         }
         {   // (quad form with 8 / 4 / 2 quads per wave: 67 / 68 / 102 us against 55 us, round 4)
             // a wave per object up to 512 objects, a 16-lane row up to 2047 (B = 100: -10 us, 512: -5, 1024: -5 with rows, +16 with waves), the quad form for launch sets
@@ -1156,6 +1080,59 @@ int launch_epnp_stages(EpnpStageArgs &ea, void *workspace, size_t workspace_byte
     rc = run();
     if (own) { const hipError_t e = hipFreeAsync(base, st); if (rc == MR_OK && e != hipSuccess) { g_last_hip_error = (int)e; rc = MR_ERR_HIP; } }
     return rc;
+}
+
+// The correspondence inputs of the per-object launches as the C ABI passes them: x2d / istd / x3d with their (b, p, c) element strides, the
+// fp32 camera matrices and u / v clip ranges (a batch of 1 is broadcast to every object).
+struct CorrIn {
+    const void *x2d; const int64_t *s2; const void *istd; const int64_t *sw; const void *x3d; const int64_t *s3;
+    const float *K; int cam_batch; const float *ur, *vr; int range_batch;
+    bool complete() const { return x2d && s2 && istd && sw && x3d && s3 && K && ur && vr; }
+    bool batches_ok(int B) const { return (cam_batch == 1 || cam_batch == B) && (range_batch == 1 || range_batch == B); }
+};
+// ... copied into a kernel's argument struct (PnpArgs, Pnp6Args, HessArgs, PnpBwdArgs: the same field names, each struct its own layout)
+template <class A>
+void set_inputs(A &a, const CorrIn &in) {
+    a.x2d = in.x2d; a.istd = in.istd; a.x3d = in.x3d;
+    for (int i = 0; i < 3; ++i) { a.s2[i] = in.s2[i]; a.sw[i] = in.sw[i]; a.s3[i] = in.s3[i]; }
+    a.K = in.K; a.K_stride = (in.cam_batch == 1) ? 0 : 9;
+    a.ur = in.ur; a.vr = in.vr; a.r_stride = (in.range_batch == 1) ? 0 : 2;
+}
+
+// The order of the istd means (MR_MEAN_* bits of a.flags; AUTO: numpy's pairwise tree where the istd rows are contiguous, always for from_head,
+// whose tile is channel-planar) and the tree's plan where the kernel forms the means itself (no external initialiser's mask).
+int choose_mean_order(PnpArgs &a) {
+    int mm = a.flags & MR_MEAN_MASK;
+    if (mm == MR_MEAN_AUTO) mm = (a.from_head || (a.sw[1] == 1 && a.P > 1)) ? MR_MEAN_PAIRWISE : MR_MEAN_SEQUENTIAL;
+    a.mean_mode = mm;
+    if (mm == MR_MEAN_PAIRWISE && !(a.flags & MR_NO_ISTD_MASK) && !a.init_mask && !build_plan(a.plan, a.P)) return MR_ERR_UNSUPPORTED;
+    return MR_OK;
+}
+
+// Grouped launches run the objects of several calls of B objects each as one batch: object i of call c is object c * B + i, and call c's pointers
+// are biased so that this GLOBAL index addresses them (EpnpCallPtrs, PnpCallTable::CallPtrs).  Optional per-call pointers (a table that may be
+// NULL, entries that may be NULL) are given for all calls or for none.
+struct CallBias {
+    int c; long long o, esize;              // the call, its first object in the batch, bytes per element of the correspondence tensors
+    CallBias(int call, int B, int in_dtype) : c(call), o((long long)call * B), esize(in_dtype == MR_F64 ? 8 : (in_dtype == MR_F32 ? 4 : 2)) {}
+    // a correspondence tensor: strides[0] elements per object
+    const void *operator()(const void *const *t, const int64_t *strides) const { return (const char *)t[c] - o * strides[0] * esize; }
+    // any other pointer, `rows` elements per object (NULL stays NULL)
+    template <typename P> P *operator()(P *const *t, long long rows) const { P *const q = t ? t[c] : nullptr; return q ? q - o * rows : nullptr; }
+    // an optional pointer given for this call and not for call 0, or the other way round
+    template <typename P> bool mixed(P *const *t) const { return (t && t[c]) != (t && t[0]); }
+};
+
+// f(TypeTag<T>{}) for the storage type of the correspondence tensors: float, __half or double
+template <typename T> struct TypeTag { using type = T; };
+template <typename F>
+int with_storage_type(int in_dtype, F &&f) {
+    switch (in_dtype) {
+        case MR_F32: return f(TypeTag<float>{});
+        case MR_F16: return f(TypeTag<__half>{});
+        case MR_F64: return f(TypeTag<double>{});
+        default: return MR_ERR_UNSUPPORTED;
+    }
 }
 
 }  // namespace
@@ -1234,36 +1211,25 @@ int mr_pnp_device_count(void) {
 }
 
 static int pnp_uncert_launch(
-    const void *x2d, const int64_t *x2d_strides, const void *istd, const int64_t *istd_strides,
-    const void *x3d, const int64_t *x3d_strides, int in_dtype,
-    const float *cam_mats, int cam_batch, const float *u_range, const float *v_range, int range_batch,
+    const CorrIn &in, int in_dtype,
     const float *ransac_thr, const double *init_pose, const uint8_t *init_mask, const uint8_t *init_valid, int B, int P,
     float z_min, float istd_thres, int inlier_opt_only, int flags,
     uint8_t *valid, float *pose, float *cov, float *tr_radius, uint8_t *inlier_mask, float *diag, void *stream,
     int ncalls = 1, const PnpCallTable::CallPtrs *calls = nullptr, const EpnpRefitIn *rf = nullptr, const float *calib_logscale = nullptr, float corr_sd = 0.0f) {
     if (B < 0 || P < 4 || P > 64 * kMaxChunks) return MR_ERR_BAD_ARGUMENT;
     if (B == 0) return MR_OK;
-    if (!x2d || !istd || !x3d || !x2d_strides || !istd_strides || !x3d_strides || !cam_mats || !u_range || !v_range ||
-        !valid || !pose || !tr_radius || (!cov && !(flags & MR_COV_NONE)))
-        return MR_ERR_BAD_ARGUMENT;
-    if ((cam_batch != 1 && cam_batch != B) || (range_batch != 1 && range_batch != B)) return MR_ERR_BAD_ARGUMENT;
+    if (!in.complete() || !valid || !pose || !tr_radius || (!cov && !(flags & MR_COV_NONE))) return MR_ERR_BAD_ARGUMENT;
+    if (!in.batches_ok(B)) return MR_ERR_BAD_ARGUMENT;
     PnpArgs a;
     memset(&a, 0, sizeof a);
-    a.x2d = x2d; a.istd = istd; a.x3d = x3d;
-    for (int i = 0; i < 3; ++i) { a.s2[i] = x2d_strides[i]; a.sw[i] = istd_strides[i]; a.s3[i] = x3d_strides[i]; }
-    a.K = cam_mats; a.K_stride = (cam_batch == 1) ? 0 : 9; a.K_f64 = 0;
-    a.ur = u_range; a.vr = v_range; a.r_stride = (range_batch == 1) ? 0 : 2; a.r_f64 = 0;
+    set_inputs(a, in);
     a.ransac_thr = ransac_thr; a.init_pose = init_pose; a.init_mask = init_mask; a.init_valid = init_valid;
     a.B = B; a.P = P; a.z_min = (double)z_min; a.istd_thres = istd_thres; a.inlier_opt_only = inlier_opt_only; a.flags = flags;
     a.valid = valid; a.pose = pose; a.cov = cov; a.tr = tr_radius; a.mask = inlier_mask; a.diag = diag;
     a.stamps = g_stamps;
     if (calib_logscale && calls && calls[0].cov_calib) { a.calib_logscale = calib_logscale; a.corr_sd = corr_sd; a.cov_calib = calls[0].cov_calib; }      // per call: the table's
-    int mm = flags & MR_MEAN_MASK;
-    if (mm == MR_MEAN_AUTO) mm = (istd_strides[1] == 1 && P > 1) ? MR_MEAN_PAIRWISE : MR_MEAN_SEQUENTIAL;
-    a.mean_mode = mm;
-    if (mm == MR_MEAN_PAIRWISE && !(flags & MR_NO_ISTD_MASK) && !init_mask) {
-        if (!build_plan(a.plan, P)) return MR_ERR_UNSUPPORTED;
-    }
+    int rc;
+    if ((rc = choose_mean_order(a)) != MR_OK) return rc;
     PnpCallTable tbl;
     memset(&tbl, 0, sizeof tbl);
     tbl.ncalls = 1; tbl.group_B = B;
@@ -1274,12 +1240,7 @@ static int pnp_uncert_launch(
     const int wpo = lm_launch_waves(a, flags, in_dtype);
     hipStream_t st = (hipStream_t)stream;
     const PnpCallTable *tp = (ncalls > 1 || rf) ? &tbl : nullptr;
-    switch (in_dtype) {
-        case MR_F32: return launch_wpo<float>(a, wpo, st, tp, rf);
-        case MR_F16: return launch_wpo<__half>(a, wpo, st, tp, rf);
-        case MR_F64: return launch_wpo<double>(a, wpo, st, tp, rf);
-        default: return MR_ERR_UNSUPPORTED;
-    }
+    return with_storage_type(in_dtype, [&](auto t) { return launch_wpo<typename decltype(t)::type>(a, wpo, st, tp, rf); });
 }
 
 int mr_pnp_uncert_batched(
@@ -1289,7 +1250,7 @@ int mr_pnp_uncert_batched(
     const float *ransac_thr, const double *init_pose, int B, int P,
     float z_min, float istd_thres, int inlier_opt_only, int flags,
     uint8_t *valid, float *pose, float *cov, float *tr_radius, uint8_t *inlier_mask, float *diag, void *stream) {
-    return pnp_uncert_launch(x2d, x2d_strides, istd, istd_strides, x3d, x3d_strides, in_dtype, cam_mats, cam_batch, u_range, v_range, range_batch,
+    return pnp_uncert_launch({ x2d, x2d_strides, istd, istd_strides, x3d, x3d_strides, cam_mats, cam_batch, u_range, v_range, range_batch }, in_dtype,
                              ransac_thr, init_pose, nullptr, nullptr, B, P, z_min, istd_thres, inlier_opt_only, flags,
                              valid, pose, cov, tr_radius, inlier_mask, diag, stream);
 }
@@ -1302,7 +1263,7 @@ int mr_pnp_uncert_from_init_batched(
     float z_min, int inlier_opt_only, int flags,
     uint8_t *valid, float *pose, float *cov, float *tr_radius, uint8_t *inlier_mask, float *diag, void *stream) {
     if (B > 0 && (!init_pose || !init_mask || !init_valid)) return MR_ERR_BAD_ARGUMENT;
-    return pnp_uncert_launch(x2d, x2d_strides, istd, istd_strides, x3d, x3d_strides, in_dtype, cam_mats, cam_batch, u_range, v_range, range_batch,
+    return pnp_uncert_launch({ x2d, x2d_strides, istd, istd_strides, x3d, x3d_strides, cam_mats, cam_batch, u_range, v_range, range_batch }, in_dtype,
                              nullptr, init_pose, init_mask, init_valid, B, P, z_min, 0.0f, inlier_opt_only, flags,
                              valid, pose, cov, tr_radius, inlier_mask, diag, stream);
 }
@@ -1322,31 +1283,25 @@ static int pnp_from_init_grouped(
     if (!x2d || !istd || !x3d || !x2d_strides || !istd_strides || !x3d_strides || !cam_mats || !u_range || !v_range || !init_pose || !init_mask || !init_valid ||
         !valid || !pose || !tr_radius || (!cov && !(flags & MR_COV_NONE))) return MR_ERR_BAD_ARGUMENT;       // (no covariance asked: the table itself may be NULL, like its entries)
     if ((long long)B * ncalls > 0x7fffffffll / kEpMaxIters) return MR_ERR_UNSUPPORTED;                         // objects are numbered through the set in int arithmetic (as in epnp_ransac_launch)
-    const bool with_mask = inlier_mask && inlier_mask[0], with_diag = diag && diag[0];
-    const size_t esize = in_dtype == MR_F64 ? 8 : (in_dtype == MR_F32 ? 4 : 2);
     const long long ks = (cam_batch == 1) ? 0 : 9, rs = (range_batch == 1) ? 0 : 2;
     PnpCallTable::CallPtrs cp[8];
     for (int c = 0; c < ncalls; ++c) {
         if (!x2d[c] || !istd[c] || !x3d[c] || !cam_mats[c] || !u_range[c] || !v_range[c] || !init_pose[c] || !init_mask[c] || !init_valid[c] ||
             !valid[c] || !pose[c] || !tr_radius[c] || (!(cov && cov[c]) && !(flags & MR_COV_NONE))) return MR_ERR_BAD_ARGUMENT;
-        if ((inlier_mask && inlier_mask[c] != nullptr) != with_mask || (diag && diag[c] != nullptr) != with_diag) return MR_ERR_BAD_ARGUMENT;      // all or none
-        // pointers biased so that the GLOBAL object index c * B + i addresses object i of call c
-        const long long o = (long long)c * B;
+        const CallBias at(c, B, in_dtype);
+        if (at.mixed(inlier_mask) || at.mixed(diag) || at.mixed(cov_calib)) return MR_ERR_BAD_ARGUMENT;       // all or none
         PnpCallTable::CallPtrs &q = cp[c];
-        q.x2d = (const char *)x2d[c] - o * x2d_strides[0] * (long long)esize;
-        q.istd = (const char *)istd[c] - o * istd_strides[0] * (long long)esize;
-        q.x3d = (const char *)x3d[c] - o * x3d_strides[0] * (long long)esize;
-        q.K = (const char *)cam_mats[c] - o * ks * 4; q.ur = (const char *)u_range[c] - o * rs * 4; q.vr = (const char *)v_range[c] - o * rs * 4;
-        q.init_pose = init_pose[c] - o * 4; q.init_mask = init_mask[c] - o * P; q.init_valid = init_valid[c] - o;
-        q.valid = valid[c] - o; q.pose = pose[c] - o * 4; q.cov = (cov && cov[c]) ? cov[c] - o * 16 : nullptr; q.tr = tr_radius[c] - o;
-        q.mask = with_mask ? inlier_mask[c] - o * P : nullptr; q.diag = with_diag ? diag[c] - o * 4 : nullptr;
-        if ((cov_calib && cov_calib[c] != nullptr) != with_calib) return MR_ERR_BAD_ARGUMENT;
-        q.cov_calib = with_calib ? cov_calib[c] - o * 16 : nullptr;
-        if (rf) rf->diag[c] = (epnp_diag && epnp_diag[c]) ? epnp_diag[c] - o * 4 : nullptr;
+        q.x2d = at(x2d, x2d_strides); q.istd = at(istd, istd_strides); q.x3d = at(x3d, x3d_strides);
+        q.K = at(cam_mats, ks); q.ur = at(u_range, rs); q.vr = at(v_range, rs);
+        q.init_pose = at(init_pose, 4); q.init_mask = at(init_mask, P); q.init_valid = at(init_valid, 1);
+        q.valid = at(valid, 1); q.pose = at(pose, 4); q.cov = at(cov, 16); q.tr = at(tr_radius, 1);
+        q.mask = at(inlier_mask, P); q.diag = at(diag, 4); q.cov_calib = at(cov_calib, 16);
+        if (rf) rf->diag[c] = at(epnp_diag, 4);
     }
-    return pnp_uncert_launch(x2d[0], x2d_strides, istd[0], istd_strides, x3d[0], x3d_strides, in_dtype, cam_mats[0], cam_batch, u_range[0], v_range[0], range_batch,
-                             nullptr, init_pose[0], init_mask[0], init_valid[0], B, P, z_min, 0.0f, inlier_opt_only, flags,
-                             valid[0], pose[0], cov ? cov[0] : nullptr, tr_radius[0], with_mask ? inlier_mask[0] : nullptr, with_diag ? diag[0] : nullptr, stream, ncalls, cp, rf, calib_logscale, corr_sd);
+    return pnp_uncert_launch({ x2d[0], x2d_strides, istd[0], istd_strides, x3d[0], x3d_strides, cam_mats[0], cam_batch, u_range[0], v_range[0], range_batch },
+                             in_dtype, nullptr, init_pose[0], init_mask[0], init_valid[0], B, P, z_min, 0.0f, inlier_opt_only, flags,
+                             valid[0], pose[0], cov ? cov[0] : nullptr, tr_radius[0], inlier_mask ? inlier_mask[0] : nullptr, diag ? diag[0] : nullptr, stream,
+                             ncalls, cp, rf, calib_logscale, corr_sd);
 }
 
 int mr_pnp_uncert_from_init_grouped(
@@ -1393,43 +1348,30 @@ static int epnp_ransac_launch(
     if (B == 0) return MR_OK;
     if ((long long)B * ncalls > 0x7fffffffll / kEpMaxIters) return MR_ERR_UNSUPPORTED;
     if (!x2d || !istd || !x3d || !x2d_strides || !istd_strides || !x3d_strides || !cam_mats || !init_pose || !init_mask || !init_valid) return MR_ERR_BAD_ARGUMENT;
-    if (cam_batch != 1 && cam_batch != B) return MR_ERR_BAD_ARGUMENT;
-    const bool with_thr = ransac_thr && ransac_thr[0], with_diag = diag && diag[0];
+    const CorrIn in{ x2d[0], x2d_strides, istd[0], istd_strides, x3d[0], x3d_strides, cam_mats[0], cam_batch, nullptr, nullptr, 1 };
+    if (!in.batches_ok(B)) return MR_ERR_BAD_ARGUMENT;
+    EpnpStageArgs sa;
+    memset(&sa, 0, sizeof sa);
     for (int c = 0; c < ncalls; ++c) {
         if (!x2d[c] || !istd[c] || !x3d[c] || !cam_mats[c] || !init_pose[c] || !init_mask[c] || !init_valid[c]) return MR_ERR_BAD_ARGUMENT;
-        if ((ransac_thr && ransac_thr[c] != nullptr) != with_thr || (diag && diag[c] != nullptr) != with_diag) return MR_ERR_BAD_ARGUMENT;     // all or none
+        const CallBias at(c, B, in_dtype);
+        if (at.mixed(ransac_thr) || at.mixed(diag)) return MR_ERR_BAD_ARGUMENT;     // all or none
+        EpnpCallPtrs &q = sa.call[c];
+        q.x2d = at(x2d, x2d_strides); q.istd = at(istd, istd_strides); q.x3d = at(x3d, x3d_strides); q.K = at(cam_mats, cam_batch == 1 ? 0 : 9);
+        q.ransac_thr = at(ransac_thr, 1);
+        q.init_pose = at(init_pose, 4); q.init_mask = at(init_mask, P); q.init_ok = at(init_valid, 1); q.diag = at(diag, 4);
     }
     if (debug_hypotheses && ncalls != 1) return MR_ERR_BAD_ARGUMENT;
     if ((flags & MR_EPNP_DEFER_REFIT) && !workspace) return MR_ERR_BAD_ARGUMENT;       // the LM launch that finishes the job needs the workspace
-    const size_t esize = in_dtype == MR_F64 ? 8 : (in_dtype == MR_F32 ? 4 : 2);
-    EpnpStageArgs sa;
-    memset(&sa, 0, sizeof sa);
     PnpArgs &a = sa.p;
-    a.x2d = x2d[0]; a.istd = istd[0]; a.x3d = x3d[0];
-    for (int i = 0; i < 3; ++i) { a.s2[i] = x2d_strides[i]; a.sw[i] = istd_strides[i]; a.s3[i] = x3d_strides[i]; }
-    a.K = cam_mats[0]; a.K_stride = (cam_batch == 1) ? 0 : 9; a.K_f64 = 0;
-    a.ransac_thr = with_thr ? ransac_thr[0] : nullptr;
+    set_inputs(a, in);
+    a.ransac_thr = ransac_thr ? ransac_thr[0] : nullptr;
     a.B = B * ncalls; a.P = P; a.istd_thres = istd_thres; a.flags = flags;
-    int mm = flags & MR_MEAN_MASK;
-    if (mm == MR_MEAN_AUTO) mm = (istd_strides[1] == 1 && P > 1) ? MR_MEAN_PAIRWISE : MR_MEAN_SEQUENTIAL;
-    a.mean_mode = mm;
-    if (mm == MR_MEAN_PAIRWISE && !(flags & MR_NO_ISTD_MASK)) {
-        if (!build_plan(a.plan, P)) return MR_ERR_UNSUPPORTED;
-    }
+    int rc;
+    if ((rc = choose_mean_order(a)) != MR_OK) return rc;
     a.stamps = g_stamps;
-    sa.init_pose = init_pose[0]; sa.init_mask = init_mask[0]; sa.init_ok = init_valid[0]; sa.diag = with_diag ? diag[0] : nullptr; sa.dbg_hyp = debug_hypotheses; sa.max_iters = max_iters;
+    sa.init_pose = init_pose[0]; sa.init_mask = init_mask[0]; sa.init_ok = init_valid[0]; sa.diag = diag ? diag[0] : nullptr; sa.dbg_hyp = debug_hypotheses; sa.max_iters = max_iters;
     sa.ncalls = ncalls; sa.group_B = B;
-    for (int c = 0; c < ncalls; ++c) {
-        // pointers biased so that the GLOBAL object index c * B + i addresses object i of call c (epnp_stages.inc EpnpCallPtrs)
-        const long long o = (long long)c * B;
-        EpnpCallPtrs &q = sa.call[c];
-        q.x2d = (const char *)x2d[c] - o * x2d_strides[0] * (long long)esize;
-        q.istd = (const char *)istd[c] - o * istd_strides[0] * (long long)esize;
-        q.x3d = (const char *)x3d[c] - o * x3d_strides[0] * (long long)esize;
-        q.K = (const char *)cam_mats[c] - o * a.K_stride * (long long)sizeof(float);
-        q.ransac_thr = with_thr ? ransac_thr[c] - o : nullptr;
-        q.init_pose = init_pose[c] - o * 4; q.init_mask = init_mask[c] - o * P; q.init_ok = init_valid[c] - o; q.diag = with_diag ? diag[c] - o * 4 : nullptr;
-    }
     hipStream_t st = (hipStream_t)stream;
     // hypotheses solved for every object before the replayed loop is consulted: MR_EPNP_FIRST_ROUND bits of `flags` (1..30), else the
     // environment variable MR_EPNP_FIRST_ROUND, else by the size of the launch set: 10 up to 2047 objects (one call at a time: the
@@ -1440,12 +1382,7 @@ static int epnp_ransac_launch(
     static const int first_env = [] { const char *e = getenv("MR_EPNP_FIRST_ROUND"); const int v = e ? atoi(e) : 0; return v < 1 ? 0 : (v > 30 ? 30 : v); }();
     const int first_bits = (flags & MR_EPNP_FIRST_ROUND_MASK) >> MR_EPNP_FIRST_ROUND_SHIFT;
     const int first_round = first_bits ? (first_bits > 30 ? 30 : first_bits) : (first_env ? first_env : ((long long)B * ncalls >= 2048 ? 3 : 10));
-    switch (in_dtype) {
-        case MR_F32: return launch_epnp_stages<float>(sa, workspace, workspace_bytes, first_round, st);
-        case MR_F16: return launch_epnp_stages<__half>(sa, workspace, workspace_bytes, first_round, st);
-        case MR_F64: return launch_epnp_stages<double>(sa, workspace, workspace_bytes, first_round, st);
-        default: return MR_ERR_UNSUPPORTED;
-    }
+    return with_storage_type(in_dtype, [&](auto t) { return launch_epnp_stages<typename decltype(t)::type>(sa, workspace, workspace_bytes, first_round, st); });
 }
 
 int mr_epnp_ransac_batched(
@@ -1490,28 +1427,18 @@ int mr_pnp6_refine_batched(
     const float *cam_mats, int cam_batch, const float *u_range, const float *v_range, int range_batch,
     const uint8_t *inlier_mask, const float *pose4, const uint8_t *valid4, int B, int P, float z_min, int flags,
     uint8_t *valid, float *pose6, float *cov6, float *diag, void *stream) {
+    const CorrIn in{ x2d, x2d_strides, istd, istd_strides, x3d, x3d_strides, cam_mats, cam_batch, u_range, v_range, range_batch };
     if (B < 0 || P < 4 || P > 64 * kMaxChunks) return MR_ERR_BAD_ARGUMENT;
     if (B == 0) return MR_OK;
-    if (!x2d || !istd || !x3d || !x2d_strides || !istd_strides || !x3d_strides || !cam_mats || !u_range || !v_range || !inlier_mask || !pose4 ||
-        !valid4 || !valid || !pose6 || !cov6)
-        return MR_ERR_BAD_ARGUMENT;
-    if ((cam_batch != 1 && cam_batch != B) || (range_batch != 1 && range_batch != B)) return MR_ERR_BAD_ARGUMENT;
+    if (!in.complete() || !inlier_mask || !pose4 || !valid4 || !valid || !pose6 || !cov6) return MR_ERR_BAD_ARGUMENT;
+    if (!in.batches_ok(B)) return MR_ERR_BAD_ARGUMENT;
     Pnp6Args a;
     memset(&a, 0, sizeof a);
-    a.x2d = x2d; a.istd = istd; a.x3d = x3d;
-    for (int i = 0; i < 3; ++i) { a.s2[i] = x2d_strides[i]; a.sw[i] = istd_strides[i]; a.s3[i] = x3d_strides[i]; }
-    a.K = cam_mats; a.K_stride = (cam_batch == 1) ? 0 : 9; a.K_f64 = 0;
-    a.ur = u_range; a.vr = v_range; a.r_stride = (range_batch == 1) ? 0 : 2; a.r_f64 = 0;
+    set_inputs(a, in);
     a.mask = inlier_mask; a.pose4 = pose4; a.valid4 = valid4;
-    a.B = B; a.P = P; a.z_min = (double)z_min;
-    { const int mi = (flags & MR_LM_MAXIT_MASK) >> MR_LM_MAXIT_SHIFT; a.lm_max_iter = mi ? mi : 50; }
+    a.B = B; a.P = P; a.z_min = (double)z_min; a.lm_max_iter = lm_max_iter(flags);
     a.valid = valid; a.pose6 = pose6; a.cov6 = cov6; a.diag = diag;
-    switch (in_dtype) {
-        case MR_F32: return launch_pnp6<float>(a, (hipStream_t)stream);
-        case MR_F16: return launch_pnp6<__half>(a, (hipStream_t)stream);
-        case MR_F64: return launch_pnp6<double>(a, (hipStream_t)stream);
-        default: return MR_ERR_UNSUPPORTED;
-    }
+    return with_storage_type(in_dtype, [&](auto t) { return launch_pnp6<typename decltype(t)::type>(a, (hipStream_t)stream); });
 }
 
 int mr_pnp_exact_hessian_batched(
@@ -1520,28 +1447,21 @@ int mr_pnp_exact_hessian_batched(
     const float *cam_mats, int cam_batch, const float *u_range, const float *v_range, int range_batch,
     const float *pose, const uint8_t *inlier_mask, int B, int P, float z_min,
     uint8_t *valid, float *hess, float *cov, void *stream) {
+    const CorrIn in{ x2d, x2d_strides, istd, istd_strides, x3d, x3d_strides, cam_mats, cam_batch, u_range, v_range, range_batch };
     if (B < 0 || P < 1) return MR_ERR_BAD_ARGUMENT;
     if (B == 0) return MR_OK;
-    if (!x2d || !istd || !x3d || !x2d_strides || !istd_strides || !x3d_strides || !cam_mats || !u_range || !v_range || !pose || !valid || !cov)
-        return MR_ERR_BAD_ARGUMENT;
-    if ((cam_batch != 1 && cam_batch != B) || (range_batch != 1 && range_batch != B)) return MR_ERR_BAD_ARGUMENT;
+    if (!in.complete() || !pose || !valid || !cov) return MR_ERR_BAD_ARGUMENT;
+    if (!in.batches_ok(B)) return MR_ERR_BAD_ARGUMENT;
     HessArgs a;
     memset(&a, 0, sizeof a);
-    a.x2d = x2d; a.istd = istd; a.x3d = x3d;
-    for (int i = 0; i < 3; ++i) { a.s2[i] = x2d_strides[i]; a.sw[i] = istd_strides[i]; a.s3[i] = x3d_strides[i]; }
-    a.K = cam_mats; a.K_stride = (cam_batch == 1) ? 0 : 9;
-    a.ur = u_range; a.vr = v_range; a.r_stride = (range_batch == 1) ? 0 : 2;
+    set_inputs(a, in);
     a.pose = pose; a.mask = inlier_mask; a.B = B; a.P = P; a.z_min = (double)z_min;
     a.valid = valid; a.hess = hess; a.cov = cov;
-    hipStream_t st = (hipStream_t)stream;
-    switch (in_dtype) {
-        case MR_F32: hipLaunchKernelGGL((exact_hessian_kernel<float>), dim3(B), dim3(256), 0, st, a); break;
-        case MR_F16: hipLaunchKernelGGL((exact_hessian_kernel<__half>), dim3(B), dim3(256), 0, st, a); break;
-        case MR_F64: hipLaunchKernelGGL((exact_hessian_kernel<double>), dim3(B), dim3(256), 0, st, a); break;
-        default: return MR_ERR_UNSUPPORTED;
-    }
-    HIP_TRY(hipGetLastError());
-    return MR_OK;
+    return with_storage_type(in_dtype, [&](auto t) {
+        hipLaunchKernelGGL((exact_hessian_kernel<typename decltype(t)::type>), dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+        return MR_OK;
+    });
 }
 
 int mr_pnp_uncert_backward_batched(
@@ -1551,31 +1471,24 @@ int mr_pnp_uncert_backward_batched(
     const float *pose, const uint8_t *inlier_mask, const uint8_t *valid, int lm_all_points,
     const float *grad_pose, const float *cov, const float *grad_cov, int B, int P, float z_min,
     float *grad_x2d, float *grad_istd, float *grad_x3d, uint8_t *status, void *stream) {
+    const CorrIn in{ x2d, x2d_strides, istd, istd_strides, x3d, x3d_strides, cam_mats, cam_batch, u_range, v_range, range_batch };
     if (B < 0 || P < 1) return MR_ERR_BAD_ARGUMENT;
     if (B == 0) return MR_OK;
-    if (!x2d || !istd || !x3d || !x2d_strides || !istd_strides || !x3d_strides || !cam_mats || !u_range || !v_range || !pose || !valid)
-        return MR_ERR_BAD_ARGUMENT;
+    if (!in.complete() || !pose || !valid) return MR_ERR_BAD_ARGUMENT;
     if ((cov == nullptr) != (grad_cov == nullptr)) return MR_ERR_BAD_ARGUMENT;
-    if ((cam_batch != 1 && cam_batch != B) || (range_batch != 1 && range_batch != B)) return MR_ERR_BAD_ARGUMENT;
+    if (!in.batches_ok(B)) return MR_ERR_BAD_ARGUMENT;
     PnpBwdArgs a;
     memset(&a, 0, sizeof a);
-    a.x2d = x2d; a.istd = istd; a.x3d = x3d;
-    for (int i = 0; i < 3; ++i) { a.s2[i] = x2d_strides[i]; a.sw[i] = istd_strides[i]; a.s3[i] = x3d_strides[i]; }
-    a.K = cam_mats; a.K_stride = (cam_batch == 1) ? 0 : 9;
-    a.ur = u_range; a.vr = v_range; a.r_stride = (range_batch == 1) ? 0 : 2;
+    set_inputs(a, in);
     a.pose = pose; a.mask = inlier_mask; a.valid = valid; a.lm_all = lm_all_points ? 1 : 0;
     a.grad_pose = grad_pose; a.cov = cov; a.grad_cov = grad_cov;
     a.B = B; a.P = P; a.z_min = (double)z_min;
     a.g2 = grad_x2d; a.gw = grad_istd; a.g3 = grad_x3d; a.status = status;
-    hipStream_t st = (hipStream_t)stream;
-    switch (in_dtype) {
-        case MR_F32: hipLaunchKernelGGL((pnp_uncert_backward_kernel<float>), dim3(B), dim3(256), 0, st, a); break;
-        case MR_F16: hipLaunchKernelGGL((pnp_uncert_backward_kernel<__half>), dim3(B), dim3(256), 0, st, a); break;
-        case MR_F64: hipLaunchKernelGGL((pnp_uncert_backward_kernel<double>), dim3(B), dim3(256), 0, st, a); break;
-        default: return MR_ERR_UNSUPPORTED;
-    }
-    HIP_TRY(hipGetLastError());
-    return MR_OK;
+    return with_storage_type(in_dtype, [&](auto t) {
+        hipLaunchKernelGGL((pnp_uncert_backward_kernel<typename decltype(t)::type>), dim3(B), dim3(256), 0, (hipStream_t)stream, a);
+        HIP_TRY(hipGetLastError());
+        return MR_OK;
+    });
 }
 
 static int fill_decode_args(DecodeArgs &a, const void *all_pred, int pred_dtype, const int64_t *labels, const uint8_t *flip, const float *dim,
@@ -1625,28 +1538,10 @@ int mr_noc_decode_batched(
     if (x4) {
         // 256 threads x one quad measured best (13.1 us per 1024 x 28x28 batch; 128 x 2 quads 14.2, 64 x 4 quads 25.5: the kernel wants threads, not trips);
         // a persistent, three-stage software-pipelined form (loads of the next quad in flight during the arithmetic; bit-identical outputs) is NOT faster:
-        // 13.0 - 14.9 us against 12.5 in the same session (tools/ubench/k2_pipelined_experiment.inc, profiles/r04_k2_pipelined_experiment.txt)
-#ifdef MR_K2_EXPERIMENT
-        {
-            static const int lds = getenv("MR_K2_LDS") ? atoi(getenv("MR_K2_LDS")) : 0;       // dynamic LDS nobody uses: caps the workgroups resident per CU
-            static const int thr = getenv("MR_K2_THREADS") ? atoi(getenv("MR_K2_THREADS")) : 256;
-            if (lds > 48 * 1024) {
-                static bool once = false;
-                if (!once) { (void)hipFuncSetAttribute((const void *)noc_decode_kernel_x4<256, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                             (void)hipFuncSetAttribute((const void *)noc_decode_kernel_x4<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                             (void)hipFuncSetAttribute((const void *)noc_decode_kernel_x4<64, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); once = true; }
-            }
-            if (thr == 64) hipLaunchKernelGGL((noc_decode_kernel_x4<64, 4>), dim3((unsigned)B), dim3(64), lds, (hipStream_t)stream, a, hw / 4, g_stamps);
-            else if (thr == 128) hipLaunchKernelGGL((noc_decode_kernel_x4<128, 2>), dim3((unsigned)B), dim3(128), lds, (hipStream_t)stream, a, hw / 4, g_stamps);
-            else hipLaunchKernelGGL((noc_decode_kernel_x4<256, 1>), dim3((unsigned)B), dim3(256), lds, (hipStream_t)stream, a, hw / 4, g_stamps);
-            HIP_TRY(hipGetLastError());
-            return MR_OK;
-        }
-#else
+        // 13.0 - 14.9 us against 12.5 in the same session (profiles/r04_k2_pipelined_experiment.txt)
         hipLaunchKernelGGL((noc_decode_kernel_x4<256, 1>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, a, hw / 4);
         HIP_TRY(hipGetLastError());
         return MR_OK;
-#endif
     }
     const long long blocks = (long long)((hw + 255) / 256) * B;
     if (blocks > 0x7fffffffLL) return MR_ERR_UNSUPPORTED;
@@ -1670,7 +1565,10 @@ int mr_pnp_from_head_batched(
     if (coord_2d_map && (map_h < 1 || map_w < 1)) return MR_ERR_BAD_ARGUMENT;
     if (B == 0) return MR_OK;
     if (!cam_mats || !u_range || !v_range || !valid || !pose || !tr_radius || (!cov && !(flags & MR_COV_NONE))) return MR_ERR_BAD_ARGUMENT;
-    if ((cam_batch != 1 && cam_batch != B) || (range_batch != 1 && range_batch != B)) return MR_ERR_BAD_ARGUMENT;
+    // the tile is built channel-planar, exactly the layout (and hence numpy summation order) the reference's head produces
+    const int64_t s2[3] = { 2LL * P, 1, P }, s3[3] = { 3LL * P, 1, P };
+    const CorrIn in{ nullptr, s2, nullptr, s2, nullptr, s3, cam_mats, cam_batch, u_range, v_range, range_batch };
+    if (!in.batches_ok(B)) return MR_ERR_BAD_ARGUMENT;
     PnpArgs a;
     memset(&a, 0, sizeof a);
     const int rc = fill_decode_args(a.dec, all_pred, pred_dtype, labels, flip, dim, dim_var, rois, B, num_classes, class_agnostic, h, w, dim_means, dim_stds,
@@ -1681,19 +1579,12 @@ int mr_pnp_from_head_batched(
     if (cov_calib && (!cov_calib_logscale || (flags & MR_COV_NONE))) return MR_ERR_BAD_ARGUMENT;
     a.calib_logscale = cov_calib_logscale; a.corr_sd = cov_corr_sd; a.cov_calib = cov_calib;
     a.from_head = 1;
-    // the tile is built channel-planar, exactly the layout (and hence numpy summation order) the reference's head produces
-    a.s2[0] = 2LL * P; a.s2[1] = 1; a.s2[2] = P; a.sw[0] = 2LL * P; a.sw[1] = 1; a.sw[2] = P; a.s3[0] = 3LL * P; a.s3[1] = 1; a.s3[2] = P;
-    a.K = cam_mats; a.K_stride = (cam_batch == 1) ? 0 : 9; a.K_f64 = 0;
-    a.ur = u_range; a.vr = v_range; a.r_stride = (range_batch == 1) ? 0 : 2; a.r_f64 = 0;
+    set_inputs(a, in);
     a.B = B; a.P = P; a.z_min = (double)z_min; a.istd_thres = istd_thres; a.inlier_opt_only = inlier_opt_only; a.flags = flags;
     a.valid = valid; a.pose = pose; a.cov = cov; a.tr = tr_radius; a.mask = inlier_mask; a.diag = diag;
     a.stamps = g_stamps;
-    int mm = flags & MR_MEAN_MASK;
-    if (mm == MR_MEAN_AUTO) mm = MR_MEAN_PAIRWISE;
-    a.mean_mode = mm;
-    if (mm == MR_MEAN_PAIRWISE && !(flags & MR_NO_ISTD_MASK)) {
-        if (!build_plan(a.plan, P)) return MR_ERR_UNSUPPORTED;
-    }
+    int r;
+    if ((r = choose_mean_order(a)) != MR_OK) return r;
     return launch_wpo<float>(a, lm_launch_waves(a, flags, MR_F32), (hipStream_t)stream);
 }
 

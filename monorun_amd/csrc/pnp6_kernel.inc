@@ -33,7 +33,7 @@ constexpr int kWpo6 = 4, kThreads6 = 64 * kWpo6;      // waves per object.  Meas
                                                       // 69 us (2-iteration object: 26 us; ~3.0 us per pass): the launch is its slowest chain AND two rounds of bulk.
                                                       // Round 3: covariance from the LM's own H (x == out at every exit: one evaluation less), one factorisation for
                                                       // the six right-hand sides, by wave 0 only: 105.6 -> 99.1 us, outputs bit-identical.
-                                                      // Tried and not kept (tools/ubench/pnp6_leader_follower_experiment.inc, numbers in its header): the 4-DoF kernel's
+                                                      // Tried and not kept: the 4-DoF kernel's
                                                       // leader / follower protocol with the totals in LDS — one round of workgroups at 128 VGPRs, 94.4 us, but a longer
                                                       // pass (2.8 -> 3.2 - 3.5 us): slower for one image's ~100 objects, where the launch is its slowest object.
                                                       // Round 5: the LM's H / g lane-packed (Eval6), the rotation, the iterate and the scaling in scalar registers:

@@ -624,22 +624,13 @@ struct alignas(sizeof(T)) Rec3 { T e[3]; };
 template <typename T, int BS = 4>
 struct Tile {
     const T *ra, *rb;
-#ifdef MR_B_PLANES      // experiment (VERDICT r4 item 3): the packed B records as three planes x[P], y[P], z[P] — conflict-free ds_read_b32 instead of ds_read_b96
-    int np;
-#endif
     __device__ __forceinline__ float u(int p) const { return (float)to_f(ra[4 * p + 0]); }
     __device__ __forceinline__ float v(int p) const { return (float)to_f(ra[4 * p + 1]); }
     __device__ __forceinline__ float wu(int p) const { return (float)to_f(ra[4 * p + 2]); }
     __device__ __forceinline__ float wv(int p) const { return (float)to_f(ra[4 * p + 3]); }
-#ifdef MR_B_PLANES
-    __device__ __forceinline__ float x(int p) const { return (float)to_f(BS == 3 ? rb[p] : rb[BS * p + 0]); }
-    __device__ __forceinline__ float y(int p) const { return (float)to_f(BS == 3 ? rb[np + p] : rb[BS * p + 1]); }
-    __device__ __forceinline__ float z(int p) const { return (float)to_f(BS == 3 ? rb[2 * np + p] : rb[BS * p + 2]); }
-#else
     __device__ __forceinline__ float x(int p) const { return (float)to_f(rb[BS * p + 0]); }
     __device__ __forceinline__ float y(int p) const { return (float)to_f(rb[BS * p + 1]); }
     __device__ __forceinline__ float z(int p) const { return (float)to_f(rb[BS * p + 2]); }
-#endif
     using Raw = TileRaw<T>;
     __device__ __forceinline__ void load(int p, Raw &r) const {
         if constexpr (BS == 4) {
@@ -647,12 +638,8 @@ struct Tile {
             r.u = a.e[0]; r.v = a.e[1]; r.wu = a.e[2]; r.wv = a.e[3]; r.x = b.e[0]; r.y = b.e[1]; r.z = b.e[2];
         } else {
             const Rec4<T> a = *(const Rec4<T> *)(ra + 4 * p);
-#ifdef MR_B_PLANES
-            r.u = a.e[0]; r.v = a.e[1]; r.wu = a.e[2]; r.wv = a.e[3]; r.x = rb[p]; r.y = rb[np + p]; r.z = rb[2 * np + p];
-#else
             const Rec3<T> b = *(const Rec3<T> *)(rb + 3 * p);
             r.u = a.e[0]; r.v = a.e[1]; r.wu = a.e[2]; r.wv = a.e[3]; r.x = b.e[0]; r.y = b.e[1]; r.z = b.e[2];
-#endif
         }
     }
     // the two weights of one correspondence from ONE read of its A record (a wave's 64 records are contiguous: conflict-free,
@@ -678,11 +665,7 @@ struct Tile {
             Rec3<T> b;
             a.e[0] = u_; a.e[1] = v_; a.e[2] = wu_; a.e[3] = wv_; b.e[0] = x_; b.e[1] = y_; b.e[2] = z_;
             *(Rec4<T> *)(const_cast<T *>(ra) + 4 * p) = a;
-#ifdef MR_B_PLANES
-            const_cast<T *>(rb)[p] = x_; const_cast<T *>(rb)[np + p] = y_; const_cast<T *>(rb)[2 * np + p] = z_;
-#else
             *(Rec3<T> *)(const_cast<T *>(rb) + 3 * p) = b;
-#endif
         }
     }
 };
@@ -709,8 +692,7 @@ __device__ __forceinline__ void eval_unpack(const Eval &e, double (&H)[10], doub
 template <int WPO, typename T>
 __device__ __forceinline__ double eval_sums(const Cam &k, double cs, double sn, double ptx, double pty, double ptz, int P,
                                             const uint16_t *list, int nlist, const TileW<T, WPO> &tl, double *red, int &flip,
-                                            unsigned long long *dbg = nullptr, const typename Tile<T>::Raw *first = nullptr,
-                                            const Rec4<T> *first_a = nullptr) {
+                                            unsigned long long *dbg = nullptr, const typename Tile<T>::Raw *first = nullptr) {
     constexpr int NT = 64 * WPO;
     double acc[kAcc];
     // The LM sees only the inlier points (pnp_uncert_cpu.py:62-66 subsets the arrays): the loop walks the
@@ -725,18 +707,7 @@ __device__ __forceinline__ double eval_sums(const Cam &k, double cs, double sn, 
         const bool act = (int)threadIdx.x < nvis;
         const int q0 = act ? (int)threadIdx.x : nvis - 1;
         typename Tile<T>::Raw ra;
-        if (first) {                                 // the lane's first-trip record, read once before the LM loop (first_record)
-#ifdef MR_FIRST_B_ONLY
-            // variant: only the B half (x, y, z) of the record and its index stay in registers across the LM (4 instead of 7
-            // VGPRs); the A half is one ds_read_b128 at a known address, issued here, ahead of its first use
-            if constexpr (sizeof(T) == 4) {
-                const Rec4<T> a4 = *first_a;             // read by the caller ahead of the sincos / the barrier: its latency is hidden
-                ra.u = a4.e[0]; ra.v = a4.e[1]; ra.wu = a4.e[2]; ra.wv = a4.e[3]; ra.x = first->x; ra.y = first->y; ra.z = first->z;
-            } else ra = *first;
-#else
-            ra = *first;
-#endif
-        }
+        if (first) ra = *first;                      // the lane's first-trip record, read once before the LM loop (first_record)
         else tl.load(list ? (int)list[q0] : q0, ra);
         const double wu0 = act ? (double)to_f(ra.wu) : 0.0, wv0 = act ? (double)to_f(ra.wv) : 0.0;
         const typename Tile<T>::Raw r0 = ra;
@@ -778,9 +749,6 @@ __device__ __forceinline__ void first_record(int P, const uint16_t *list, int nl
     const int nvis = list ? nlist : P;
     const int q0 = ((int)threadIdx.x < nvis) ? (int)threadIdx.x : (nvis > 0 ? nvis - 1 : 0);
     tl.load(list ? (int)list[q0] : q0, r);
-#ifdef MR_FIRST_B_ONLY
-    if constexpr (sizeof(T) == 4) { r.wv = (T)__int_as_float(list ? (int)list[q0] : q0); r.u = r.v = r.wu = T(0.0f); }      // fp32 storage: the index rides in the wv slot
-#endif
 }
 
 // Leader / follower protocol of the LM (WPO > 1).  Everything that is uniform per object — the 4x4 solve, Ceres' step
@@ -798,15 +766,7 @@ __device__ __forceinline__ void evaluate(const Cam &k, const double (&x)[4], int
                                          unsigned long long *dbg = nullptr, const typename Tile<T>::Raw *first = nullptr) {
     double sn, cs;
     if (dbg && threadIdx.x == 0) dbg[0] = __builtin_readcyclecounter();
-    Rec4<T> a4;
-#ifdef MR_FIRST_B_ONLY
-    if constexpr (sizeof(T) == 4) { if (first) a4 = *(const Rec4<T> *)(tl.ra + 4 * __float_as_int((float)to_f(first->wv))); }
-#endif
-#ifdef MR_LIBM_SINCOS
-    sincos(x[0], &sn, &cs);
-#else
     fast_sincos(x[0], sn, cs);
-#endif
     sn = uni(sn); cs = uni(cs);
     const double ptx = uni(x[1]), pty = uni(x[2]), ptz = uni(x[3]);
     if (LEAD && WPO > 1) {
@@ -814,7 +774,7 @@ __device__ __forceinline__ void evaluate(const Cam &k, const double (&x)[4], int
         __syncthreads();
     }
     if (dbg && threadIdx.x == 0) dbg[1] = __builtin_readcyclecounter();
-    e.v = eval_sums<WPO, T>(k, cs, sn, ptx, pty, ptz, P, list, nlist, tl, red, flip, dbg, first, &a4);
+    e.v = eval_sums<WPO, T>(k, cs, sn, ptx, pty, ptz, P, list, nlist, tl, red, flip, dbg, first);
     if (dbg && threadIdx.x == 0) dbg[3] = __builtin_readcyclecounter();
     e.cost = uni(0.5 * eval_get(e, 13));
     e.ok = __ballot(!isfinite(e.v)) == 0ull;                       // lanes >= kAcc hold 0
@@ -827,15 +787,11 @@ __device__ __forceinline__ void lm_follow(const Cam &k, int P, const uint16_t *l
     typename Tile<T>::Raw rec0;
     first_record<WPO, T>(P, list, nlist, tl, rec0);
     for (;;) {
-        Rec4<T> a4;
-#ifdef MR_FIRST_B_ONLY
-        if constexpr (sizeof(T) == 4) a4 = *(const Rec4<T> *)(tl.ra + 4 * __float_as_int((float)to_f(rec0.wv)));      // ahead of the barrier
-#endif
         __syncthreads();
         const double go = uni(smsg[0]);
         const double m1 = uni(smsg[1]), m2 = uni(smsg[2]), m3 = uni(smsg[3]), m4 = uni(smsg[4]), m5 = uni(smsg[5]);
         if (go == 0.0) { xfin[0] = m1; xfin[1] = m2; xfin[2] = m3; xfin[3] = m4; pose_ok = m5 != 0.0; return; }
-        (void)eval_sums<WPO, T>(k, m1, m2, m3, m4, m5, P, list, nlist, tl, red, flip, nullptr, &rec0, &a4);
+        (void)eval_sums<WPO, T>(k, m1, m2, m3, m4, m5, P, list, nlist, tl, red, flip, nullptr, &rec0);
     }
 }
 

@@ -11,13 +11,13 @@
     int flip = 0;                                       // which half of the cross-wave reduction scratch is next
 
     extern __shared__ __align__(16) unsigned char smem[];
-    // cycle stamps: development builds only (-DMR_DEBUG_STAMPS, tools/gpu_stages.py); release builds carry no stamp code
+    // cycle stamps: development builds only (-DMR_DEBUG_STAMPS, tools/gpu_leader_timeline.py); release builds carry no stamp code
 #ifdef MR_DEBUG_STAMPS
 #define MR_STAMP(i) do { if (a.stamps && tid == 0) a.stamps[(long long)b * 24 + (i)] = __builtin_readcyclecounter(); } while (0)
     unsigned long long *const dbg_lm = a.stamps ? a.stamps + (long long)b * 24 + 12 : nullptr;
     if (a.stamps && tid == 0) a.stamps[(long long)b * 24 + 8] = wall_clock64();      // 100 MHz constant clock
 #else
-#ifdef MR_EXIT_AFTER        // development aid (tools/stage_cost.sh): stop after stage MR_EXIT_AFTER, to difference instruction counts / times per stage
+#ifdef MR_EXIT_AFTER        // development aid (tools/stage_instructions.sh): stop after stage MR_EXIT_AFTER, to difference instruction counts / times per stage
 #define MR_STAMP(i) do { if ((i) == MR_EXIT_AFTER) return; } while (0)
 #else
 #define MR_STAMP(i) do { } while (0)
@@ -36,9 +36,6 @@
     unsigned char *tile_base = (unsigned char *)(sres + 4);
     TileW<T, WPO> tl;                                                        // [P] A records, [P] B records (16 or 12 bytes at fp32)
     tl.ra = (const T *)tile_base; tl.rb = (const T *)tile_base + (size_t)4 * P;
-#ifdef MR_B_PLANES
-    tl.np = P;
-#endif
     constexpr bool ONE_LIST = WPO <= 2;                                      // one- and two-wave instantiations: the final inlier list replaces the candidate list
     uint16_t *slist = (uint16_t *)(tile_base + (size_t)(4 + tile_bs<T, WPO>()) * P * sizeof(T));    // [P] candidate list
     uint16_t *slist2 = ONE_LIST ? slist : slist + ((P + 7) & ~7);             // [P] final inlier list
@@ -578,11 +575,7 @@
 #pragma clang fp contract(off)
             const double yaw = (double)posef[0], tx = (double)posef[1], ty = (double)posef[2], tz = (double)posef[3];
             double sn, cs;
-#ifdef MR_LIBM_SINCOS
-            sincos(yaw, &sn, &cs);
-#else
             spec_sincos(yaw, sn, cs);
-#endif
             double Kd[9];                                    // from LDS (parked by the prologue): not kept live across the LM loop
 #pragma unroll
             for (int i = 0; i < 9; ++i) Kd[i] = smsg[8 + i];

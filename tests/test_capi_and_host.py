@@ -152,6 +152,104 @@ def test_capi_argument_validation_without_a_gpu():
     assert lib.mr_nms_bev_batched(p, p, p, 1, 4096, 0.1, p, p, None) == -2
     assert lib.mr_nms_bev_batched(p, p, None, 1, 8, 0.1, p, p, None) == -1
 
+    # The other batched entry points: which code each bad argument gets, and which check comes first.  Every call below is refused
+    # before a kernel is launched (a workspace is never both large enough and given: nothing here may reach the GPU).
+    F32, F64, COV_NONE = _lib.MR_F32, _lib.MR_F64, _lib.MR_COV_NONE
+    tables = []
+
+    def calls(*v):                                            # a per-call pointer table of the grouped entry points
+        t = (ctypes.c_void_p * len(v))(*v)
+        tables.append(t)
+        return ctypes.addressof(t)
+    full = calls(*[p] * 8)
+    big = 0x7fffffff // 30 + 1                                # objects of a launch set are numbered in int arithmetic: too many
+
+    def icall(B=4, P=784, x2d=p, strides=st, init=p, cam_batch=1, range_batch=1, cov=p, dtype=F32, flags=0):
+        return lib.mr_pnp_uncert_from_init_batched(x2d, strides, p, st, p, st, dtype, p, cam_batch, p, p, range_batch, init, p, p, B, P,
+                                                   0.5, 1, flags, p, p, cov, p, p, None, None)
+    assert icall(B=0) == 0 and icall(B=0, init=None, x2d=None) == 0
+    assert icall(B=-1) == -1 and icall(B=-1, init=None) == -1 and icall(B=0, P=3) == -1 and icall(P=3) == -1 and icall(P=10 ** 6) == -1
+    assert icall(init=None) == -1 and icall(x2d=None) == -1 and icall(strides=None) == -1 and icall(cov=None) == -1
+    assert icall(cam_batch=3) == -1 and icall(range_batch=2) == -1 and icall(cam_batch=3, dtype=7) == -1
+    assert icall(dtype=7) == -2 and icall(cov=None, flags=COV_NONE, dtype=7) == -2 and icall(cam_batch=4, range_batch=4, dtype=7) == -2
+    assert icall(P=8192) == -2
+
+    def gcall(n=2, B=4, P=784, x2d=full, cov=full, mask=None, diag=None, cam_batch=1, range_batch=1, dtype=F32, flags=0):
+        return lib.mr_pnp_uncert_from_init_grouped(n, x2d, st, full, st, full, st, dtype, full, cam_batch, full, full, range_batch,
+                                                   full, full, full, B, P, 0.5, 1, flags, full, full, cov, full, mask, diag, None)
+    assert gcall(B=0) == 0 and gcall(B=0, P=3, x2d=None) == 0                  # an empty set succeeds before P is looked at
+    assert gcall(n=0) == -1 and gcall(n=9) == -1 and gcall(n=0, B=0) == -1 and gcall(B=-1) == -1
+    assert gcall(x2d=None) == -1 and gcall(x2d=calls(p, None)) == -1 and gcall(cov=None) == -1 and gcall(cov=calls(p, None)) == -1
+    assert gcall(B=big, x2d=calls(None, None)) == -2 and gcall(B=big, P=3) == -2    # the set's size before the calls' pointers and P
+    assert gcall(mask=calls(p, None)) == -1 and gcall(mask=calls(None, p)) == -1 and gcall(diag=calls(p, None)) == -1
+    assert gcall(P=3) == -1 and gcall(P=10 ** 6) == -1 and gcall(cam_batch=3) == -1 and gcall(range_batch=2) == -1
+    assert gcall(dtype=7) == -2 and gcall(dtype=7, mask=full, diag=calls(None, None)) == -2 and gcall(P=8192) == -2
+    assert gcall(dtype=7, cov=calls(p, None), flags=COV_NONE) == -2
+
+    wb = lib.mr_epnp_workspace_bytes(8, 784)
+
+    def fcall(n=2, B=4, P=784, x2d=full, work=p, nbytes=wb - 1, epdiag=None, logscale=None, calib=None, dtype=F32, flags=0):
+        return lib.mr_pnp_uncert_from_epnp_grouped(n, x2d, st, full, st, full, st, dtype, full, 1, full, full, 1, full, full, full, epdiag, B, P,
+                                                   0.5, 1, flags, full, full, full, full, None, None, logscale, 0.1, calib, work, nbytes, None)
+    assert fcall(B=0) == 0 and fcall(B=0, work=None, x2d=None) == 0
+    assert fcall(n=0) == -1 and fcall(n=9) == -1 and fcall(B=-1) == -1 and fcall(P=3) == -1 and fcall(B=0, P=3) == -1
+    assert fcall(B=big, work=None) == -2 and fcall(work=None) == -1 and fcall() == -1                    # no / short workspace
+    assert fcall(dtype=7) == -1 and fcall(dtype=7, nbytes=wb) == -2                                      # the workspace before the dtype
+    assert fcall(nbytes=wb, calib=full) == -1 and fcall(nbytes=wb, calib=full, logscale=p, flags=COV_NONE) == -1
+    assert fcall(nbytes=wb, calib=calls(p, None), logscale=p) == -1 and fcall(nbytes=wb, calib=calls(None, p), logscale=p) == -1
+    assert fcall(nbytes=wb, x2d=None) == -1 and fcall(nbytes=wb, x2d=calls(p, None)) == -1
+    assert fcall(P=10 ** 6, nbytes=lib.mr_epnp_workspace_bytes(8, 10 ** 6)) == -1
+    assert fcall(dtype=7, nbytes=wb, epdiag=calls(p, None)) == -2 and fcall(dtype=7, nbytes=wb, calib=full, logscale=p) == -2
+    assert fcall(P=8192, nbytes=lib.mr_epnp_workspace_bytes(8, 8192)) == -2
+
+    def rcall(n=2, B=4, P=784, x2d=full, cam_batch=1, thr=full, diag=None, max_iters=30, work=p, dtype=F32, flags=0):
+        return lib.mr_epnp_ransac_grouped(n, x2d, st, full, st, full, st, dtype, full, cam_batch, thr, B, P, 0.6, flags, max_iters,
+                                          full, full, full, diag, work, 0, None)
+    assert rcall(B=0) == 0 and rcall(B=0, x2d=None) == 0
+    assert rcall(n=0) == -1 and rcall(n=9) == -1 and rcall(n=0, B=0) == -1 and rcall(B=-1) == -1 and rcall(B=0, P=3) == -1
+    assert rcall(P=3) == -1 and rcall(P=10 ** 6) == -1 and rcall(max_iters=0) == -1 and rcall(max_iters=31) == -1
+    assert rcall(B=big, x2d=None) == -2 and rcall(x2d=None) == -1 and rcall(x2d=calls(p, None)) == -1 and rcall(cam_batch=3) == -1
+    assert rcall(thr=calls(p, None)) == -1 and rcall(thr=calls(None, p)) == -1 and rcall(diag=calls(p, None)) == -1
+    assert rcall(work=None, flags=_lib.MR_EPNP_DEFER_REFIT) == -1
+    assert rcall(dtype=7) == -2 and rcall(dtype=7, thr=None, diag=calls(None, None)) == -2 and rcall(dtype=7, cam_batch=4) == -2
+    assert rcall() == -1                                                                                  # short workspace
+
+    def p6(B=4, P=784, x2d=p, mask=p, cov6=p, cam_batch=1, range_batch=1, dtype=F32):
+        return lib.mr_pnp6_refine_batched(x2d, st, p, st, p, st, dtype, p, cam_batch, p, p, range_batch, mask, p, p, B, P, 0.5, 0, p, p, cov6, None, None)
+    assert p6(B=0) == 0 and p6(B=0, x2d=None) == 0
+    assert p6(B=-1) == -1 and p6(P=3) == -1 and p6(B=0, P=3) == -1 and p6(P=10 ** 6) == -1
+    assert p6(x2d=None) == -1 and p6(mask=None) == -1 and p6(cov6=None) == -1 and p6(cam_batch=3) == -1 and p6(range_batch=2) == -1
+    assert p6(dtype=7) == -2 and p6(P=8192) == -2 and p6(P=8192, dtype=F64) == -2
+
+    def hs(B=4, P=784, x2d=p, pose=p, mask=p, hess=p, cov=p, cam_batch=1, range_batch=1, dtype=F32):
+        return lib.mr_pnp_exact_hessian_batched(x2d, st, p, st, p, st, dtype, p, cam_batch, p, p, range_batch, pose, mask, B, P, 0.5, p, hess, cov, None)
+    assert hs(B=0) == 0 and hs(B=0, pose=None) == 0
+    assert hs(B=-1) == -1 and hs(P=0) == -1 and hs(B=0, P=0) == -1
+    assert hs(x2d=None) == -1 and hs(pose=None) == -1 and hs(cov=None) == -1 and hs(cam_batch=3) == -1 and hs(range_batch=2) == -1
+    assert hs(dtype=7) == -2 and hs(dtype=7, P=1, mask=None, hess=None) == -2
+
+    def bw(B=4, P=784, x2d=p, pose=p, valid=p, cov=None, gcov=None, cam_batch=1, range_batch=1, dtype=F32):
+        return lib.mr_pnp_uncert_backward_batched(x2d, st, p, st, p, st, dtype, p, cam_batch, p, p, range_batch, pose, p, valid, 1, p, cov, gcov,
+                                                  B, P, 0.5, p, p, p, p, None)
+    assert bw(B=0) == 0 and bw(B=0, cov=p) == 0
+    assert bw(B=-1) == -1 and bw(P=0) == -1 and bw(B=0, P=0) == -1
+    assert bw(x2d=None) == -1 and bw(pose=None) == -1 and bw(valid=None) == -1 and bw(pose=None, cov=p, gcov=p) == -1
+    assert bw(cov=p) == -1 and bw(gcov=p) == -1 and bw(cov=p, gcov=p, cam_batch=3) == -1 and bw(range_batch=2) == -1
+    assert bw(dtype=7) == -2 and bw(dtype=7, cov=p, gcov=p) == -2
+
+    def hd(B=4, h=28, w=28, pred=p, pred_dtype=F32, C=3, cam=p, cam_batch=1, range_batch=1, cov=p, flags=0, map2d=None, map_h=0,
+           logscale=None, calib=None):
+        return lib.mr_pnp_from_head_batched(pred, pred_dtype, p, p, p, None, p, B, C, 0, h, w, p, p, p, p, 1.0, 1.0, 1.0, 1.0, 0.1,
+                                            cam, cam_batch, p, p, range_batch, 0.5, 0.6, 1, flags, p, p, cov, p, p, None,
+                                            None, None, map2d, map_h, map_h, logscale, 0.1, calib, None)
+    assert hd(B=0) == 0 and hd(B=0, pred=None, cam=None) == 0
+    assert hd(B=-1) == -1 and hd(h=1, w=3) == -1 and hd(B=0, h=1, w=3) == -1 and hd(h=128, w=128) == -1
+    assert hd(map2d=p, map_h=0) == -1 and hd(B=0, map2d=p, map_h=0) == -1
+    assert hd(cam=None) == -1 and hd(cov=None) == -1 and hd(cam_batch=3) == -1 and hd(range_batch=2) == -1
+    assert hd(C=0) == -1 and hd(pred=None) == -1 and hd(pred_dtype=7) == -2 and hd(pred_dtype=7, cam_batch=3) == -1
+    assert hd(calib=p) == -1 and hd(calib=p, logscale=p, flags=COV_NONE) == -1 and hd(calib=p, pred_dtype=7) == -2
+    assert hd(h=64, w=128) == -2
+
 
 def test_img_shape_and_flip_forms_the_pipeline_passes():
     """mmdet hands img_meta['img_shape'] = (H, W, 3) and a per-image bool flip (Python or numpy bool, or a 0-dim tensor):
