@@ -8,16 +8,18 @@ There is NO CPU fallback: if the library is missing or no HIP device is present 
 import ctypes
 import glob
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 SRC = os.path.join(_HERE, 'csrc', 'monorun_pnp.hip')
 INCLUDE = os.path.join(_ROOT, 'include')
+HEADER = os.path.join(INCLUDE, 'monorun_pnp.h')
 SO = os.environ.get('MR_PNP_SO') or os.path.join(_HERE, 'libmonorun_pnp.so')     # MR_PNP_SO: A/B-test another build of the library
 
 MR_F32, MR_F16, MR_F64, MR_BF16 = 0, 1, 2, 3
-MR_MEAN_AUTO, MR_MEAN_SEQUENTIAL, MR_MEAN_PAIRWISE = 0, 1, 2
+MR_MEAN_AUTO, MR_MEAN_SEQUENTIAL, MR_MEAN_PAIRWISE, MR_MEAN_MASK = 0, 1, 2, 3          # MR_MEAN_MASK: the two bits of the istd mean's order
 MR_NO_ISTD_MASK, MR_COV_NONE, MR_COV_CERES, MR_ANY_ORDER = 0x4, 0x8, 0x10, 0x20
 MR_EPNP_REFIT_F32 = 0x40
 MR_EPNP_DEFER_REFIT = 0x80
@@ -37,7 +39,7 @@ def _stale():
         return True
     t = os.path.getmtime(SO)
     csrc = os.path.join(_HERE, 'csrc')
-    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [os.path.join(INCLUDE, 'monorun_pnp.h')]
+    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -54,8 +56,83 @@ def build(force=False, verbose=False):
     return SO
 
 
+def header_prototypes(path=HEADER):
+    """[(name, 'return type', ['arg type name', ...])] for every function the header declares."""
+    src = open(path).read()
+    src = re.sub(r'/\*.*?\*/', ' ', src, flags=re.S)
+    src = re.sub(r'//[^\n]*', ' ', src)
+    src = '\n'.join(l for l in src.split('\n') if not l.lstrip().startswith('#') and 'extern "C"' not in l and l.strip() != '}')
+    out = []
+    for m in re.finditer(r'([A-Za-z_][\w\s\*]*?)\b(\w+)\s*\(([^()]*)\)\s*;', src):
+        ret, name, args = ' '.join(m.group(1).split()), m.group(2), m.group(3)
+        args = [' '.join(a.split()).replace('* ', '*') for a in args.split(',')] if args.strip() not in ('', 'void') else []
+        out.append((name, ret, args))
+    return out
+
+
+_CTYPES = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64}
+_prototypes = None
+
+
+def _ctype(name, ctype):
+    """The ctypes type of a C type of the header.  A type this table does not know is an error, not a guess."""
+    if '*' in ctype:
+        return ctypes.c_void_p
+    if ctype not in _CTYPES:
+        raise TypeError(f'{name}: include/monorun_pnp.h uses the type {ctype!r}, which the loader has no ctypes mapping for')
+    return _CTYPES[ctype]
+
+
+def _prototype(fn):
+    """(restype, [argtypes], (argument names without the trailing stream), (names of the per-call pointer tables `T *const *`),
+    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h declares it.  The header is read once."""
+    global _prototypes
+    if _prototypes is None:
+        protos = {}
+        for name, ret, args in header_prototypes():
+            if not name.startswith('mr_'):
+                continue                                # the reference's cffi symbols of ext.h: declared by hand in load()
+            decl = [re.fullmatch(r'(.*?)(\w+)', a).groups() for a in args]
+            names = tuple(n for _, n in decl)
+            assert len(set(names)) == len(names), f'{name}: argument names repeat'
+            protos[name] = (ctypes.c_char_p if ret == 'const char *' else _ctype(name, ret),
+                            [_ctype(name, t.replace('const', '').strip()) for t, _ in decl],
+                            names[:-1] if names[-1:] == ('stream',) else names, tuple(n for t, n in decl if t.count('*') == 2), frozenset(names))
+        _prototypes = protos
+    return _prototypes[fn]
+
+
+def arg_names(fn):
+    """The argument names of an entry point in ABI order, without the trailing `stream`."""
+    return _prototype(fn)[2]
+
+
+def table_args(fn):
+    """The arguments a grouped entry point takes as per-call pointer tables (`T *const *`: one pointer per member)."""
+    return _prototype(fn)[3]
+
+
+def pack(fn, common={}, /, **named):
+    """The argument list of `lib.<fn>(*args, stream)` in ABI order from arguments given by the header's names.  `common`: a dict the
+    names missing from `named` are taken from (it may hold more than `fn` declares: another prototype's arguments, say).  TypeError
+    for a name in `named` that `fn` does not declare and for a declared one that neither gives."""
+    names = arg_names(fn)
+    if not named.keys() <= _prototype(fn)[4]:
+        raise TypeError(f'{fn}: unknown argument {sorted(set(named) - set(names))}')
+    try:
+        return [named[n] if n in named else common[n] for n in names]
+    except KeyError as e:
+        raise TypeError(f'{fn}: missing argument {e}') from None
+
+
+def ptr(t):
+    """data_ptr() of an optional tensor (None: a NULL argument)."""
+    return t.data_ptr() if t is not None else None
+
+
 def load():
-    """Return the ctypes handle; raises if the library has not been built."""
+    """Return the ctypes handle; raises if the library has not been built.  restype / argtypes of every `mr_*` entry point come
+    from its prototype in include/monorun_pnp.h (``_prototype``)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -64,99 +141,26 @@ def load():
             f'{SO} is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
             '(hipcc --offload-arch=gfx950). monorun_amd has no CPU fallback.')
     lib = ctypes.CDLL(SO)
-    vp, i32, f32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    i64p = ctypes.POINTER(ctypes.c_int64)
-    lib.mr_pnp_version.restype = i32
-    lib.mr_pnp_error_string.restype = ctypes.c_char_p
-    lib.mr_pnp_error_string.argtypes = [i32]
-    lib.mr_pnp_last_hip_error.restype = i32
-    lib.mr_pnp_device_count.restype = i32
-    lib.mr_spin.restype = i32
-    lib.mr_pick_waves.restype = i32
-    lib.mr_pick_waves.argtypes = [i32, i32]
-    lib.mr_spin.argtypes = [i32, vp]
+    vp, i32 = ctypes.c_void_p, ctypes.c_int
+    for name, _, _ in header_prototypes():
+        if name.startswith('mr_'):
+            f = getattr(lib, name)
+            f.restype, argtypes = _prototype(name)[:2]
+            if argtypes:
+                f.argtypes = argtypes
     # development aids for the tests (not in the public header, not in EXPORTED_SYMBOLS)
     lib.mr_debug_launch_waves.restype = i32
     lib.mr_debug_launch_waves.argtypes = [i32, i32, i32, i32, i32]
     lib.mr_debug_block_sum.restype = i32
     lib.mr_debug_block_sum.argtypes = [i32, vp, vp, vp]
-    lib.mr_pnp_uncert_batched.restype = i32
-    lib.mr_pnp_uncert_batched.argtypes = [
-        vp, i64p, vp, i64p, vp, i64p, i32,          # x2d, istd, x3d (+strides), in_dtype
-        vp, i32, vp, vp, i32,                       # cam_mats, cam_batch, u_range, v_range, range_batch
-        vp, vp, i32, i32,                           # ransac_thr, init_pose, B, P
-        f32, f32, i32, i32,                         # z_min, istd_thres, inlier_opt_only, flags
-        vp, vp, vp, vp, vp, vp, vp]                 # valid, pose, cov, tr, mask, diag, stream
-    lib.mr_epnp_ransac_batched.restype = i32
-    lib.mr_epnp_ransac_batched.argtypes = [vp, i64p, vp, i64p, vp, i64p, i32, vp, i32, vp, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.mr_epnp_ransac_grouped.restype = i32
-    lib.mr_epnp_ransac_grouped.argtypes = [i32, vp, i64p, vp, i64p, vp, i64p, i32, vp, i32, vp, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.mr_epnp_workspace_bytes.restype = ctypes.c_size_t
-    lib.mr_epnp_workspace_bytes.argtypes = [i32, i32]
-    lib.mr_pnp_uncert_from_init_batched.restype = i32
-    lib.mr_pnp_uncert_from_init_batched.argtypes = [vp, i64p, vp, i64p, vp, i64p, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, i32,
-                                                    vp, vp, vp, vp, vp, vp, vp]
-    lib.mr_pnp_uncert_from_init_grouped.restype = i32
-    lib.mr_pnp_uncert_from_init_grouped.argtypes = [i32, vp, i64p, vp, i64p, vp, i64p, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, i32,
-                                                    vp, vp, vp, vp, vp, vp, vp]
-    lib.mr_pnp_uncert_from_epnp_grouped.restype = i32
-    lib.mr_pnp_uncert_from_epnp_grouped.argtypes = [i32, vp, i64p, vp, i64p, vp, i64p, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, f32, i32, i32,
-                                                    vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, ctypes.c_size_t, vp]
-    lib.mr_cov_symeig_rule.restype = i32
-    lib.mr_cov_symeig_rule.argtypes = [vp, vp, i32, vp, vp]
-    lib.mr_pnp_exact_hessian_batched.restype = i32
-    lib.mr_pnp_exact_hessian_batched.argtypes = [vp, i64p, vp, i64p, vp, i64p, i32, vp, i32, vp, vp, i32, vp, vp, i32, i32, f32, vp, vp, vp, vp]
-    lib.mr_pnp_uncert_backward_batched.restype = i32
-    lib.mr_pnp_uncert_backward_batched.argtypes = [vp, i64p, vp, i64p, vp, i64p, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32,
-                                                   vp, vp, vp, vp, vp]
-    lib.mr_pnp6_refine_batched.restype = i32
-    lib.mr_pnp6_refine_batched.argtypes = [vp, i64p, vp, i64p, vp, i64p, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, f32, i32, vp, vp, vp, vp, vp]
+    # the reference's cffi signatures (ext.h): callers pass typed pointers
     dp = ctypes.POINTER(ctypes.c_double)
     lib.pnp_uncert.restype = None
     lib.pnp_uncert.argtypes = [dp, dp, dp, dp, dp, ctypes.POINTER(i32), dp, dp, dp, i32, dp]
-    if hasattr(lib, 'mr_noc_decode_batched'):
-        lib.mr_noc_decode_batched.restype = i32
-        lib.mr_noc_decode_batched.argtypes = [
-            vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
-            vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, f32, f32,
-            vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    lib.mr_pnp_from_head_batched.restype = i32
-    lib.mr_pnp_from_head_batched.argtypes = [
-        vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
-        vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_double, f32, f32,
-        vp, i32, vp, vp, i32, f32, f32, i32, i32,
-        vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, f32, vp, vp]
-    lib.mr_roi_align_avg.restype = i32
-    lib.mr_roi_align_avg.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp, vp]
     for name in ('pnp_noc_uncert', 'pnp_noc_cov_uncert'):
         f = getattr(lib, name)
         f.restype = None
         f.argtypes = [dp, dp, dp, dp, dp, dp, dp, ctypes.POINTER(i32), dp, i32, dp, ctypes.c_double]
-    lib.mr_pnp_noc_batched.restype = i32
-    lib.mr_pnp_noc_batched.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, ctypes.c_double, i32, i32, vp, vp, vp, vp]
-    lib.mr_nms_bev_batched.restype = i32
-    lib.mr_nms_bev_batched.argtypes = [vp, vp, vp, i32, i32, f32, vp, vp, vp]
-    i64 = ctypes.c_int64
-    lib.mr_bbox3d_overlaps_aligned.restype = i32
-    lib.mr_bbox3d_overlaps_aligned.argtypes = [vp, i64, vp, i64, i32, i32, i32, f32, i32, vp, vp, vp]
-    lib.mr_uncert_projection.restype = i32
-    lib.mr_uncert_projection.argtypes = [vp, vp, i64, vp, vp, i32, i32, f32, f32, vp, vp]
-    lib.mr_uncert_projection_backward.restype = i32
-    lib.mr_uncert_projection_backward.argtypes = [vp, vp, i64, vp, vp, i32, i32, f32, f32, vp, vp, vp]
-    f64 = ctypes.c_double
-    lib.mr_robust_kl_workspace_bytes.restype = i64
-    lib.mr_robust_kl_workspace_bytes.argtypes = [i64]
-    lib.mr_robust_kl_loss.restype = i32
-    lib.mr_robust_kl_loss.argtypes = [vp, vp, i64, i32, f64, f64, f64, i32, i32, f64, vp, vp, vp, vp, i64, vp]
-    lib.mr_robust_kl_loss_backward.restype = i32
-    lib.mr_robust_kl_loss_backward.argtypes = [vp, vp, i64, i32, f64, f64, i32, f64, vp, vp, vp, vp, vp]
-    lib.mr_kitti_overlaps.restype = i32
-    lib.mr_kitti_overlaps.argtypes = [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp, vp]
-    lib.mr_kitti_match_workspace_bytes.restype = i64
-    lib.mr_kitti_match_workspace_bytes.argtypes = [i32, i32]
-    lib.mr_kitti_match.restype = i32
-    lib.mr_kitti_match.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, i64,
-                                   vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     _lib = lib
     return lib
 

@@ -22,9 +22,74 @@ _DTYPES = {torch.float32: _lib.MR_F32, torch.float16: _lib.MR_F16, torch.float64
 # differ from the reference flow's on ~13 % of the objects) is an explicit fast mode since round 5.
 DEFAULT_INITIALISER = 'epnp'
 
+# the bits of a call's flags that the initialiser reads
+_INIT_FLAGS = _lib.MR_MEAN_MASK | _lib.MR_NO_ISTD_MASK | _lib.MR_EPNP_REFIT_F32 | _lib.MR_EPNP_CV_EARLY_RETURN
+
 
 def _strides(t):
     return (ctypes.c_int64 * 3)(*t.stride())
+
+
+def _first_round_flags(flags, first_round):
+    """`flags` with first_round (None: as it is) in its first-round field: the hypotheses solved for every object before the replayed loop
+    is consulted (1..30; result-neutral)."""
+    if first_round is None:
+        return int(flags)
+    return (int(flags) & ~(0x1F << _lib.MR_EPNP_FIRST_ROUND_SHIFT)) | (max(1, min(30, int(first_round))) << _lib.MR_EPNP_FIRST_ROUND_SHIFT)
+
+
+def _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range=None, v_range=None, ransac_thr=None, init_pose=None, no_gpu=None,
+            prepared=False):
+    """The inputs every entry point shares.  Returns (dev, B, P, common, keep): `common` = the arguments the prototypes share, under the
+    header's names (x2d ... in_dtype, cam_mats, cam_batch and, with u_range / v_range, those and range_batch), for ``_lib.pack``; `keep` = the
+    tensors they point into plus ransac_thr f32 (n,) | None and init_pose f64 (n,4) | None, which whoever launches must keep alive.
+    The coordinate tensors are detached and converted to the storage dtype (their own where the kernels read it, else float32) on the
+    device of coords_2d; prepared=True (the launch classes) asserts their dtypes instead and aliases the caller's buffers.
+    no_gpu: the RuntimeError message when coords_2d is not on a HIP device (None: not checked here)."""
+    dev = coords_2d.device
+    if no_gpu is not None and dev.type != 'cuda':
+        raise RuntimeError(no_gpu)
+    B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
+    if prepared:
+        assert coords_2d.dtype in _DTYPES and coords_2d_istd.dtype == coords_2d.dtype == coords_3d.dtype
+        x2d, istd, x3d = coords_2d, coords_2d_istd, coords_3d
+    else:
+        dt = coords_2d.dtype if coords_2d.dtype in _DTYPES else torch.float32
+        prep = lambda t: t.detach() if (t.dtype == dt and t.device == dev) else t.detach().to(device=dev, dtype=dt)
+        x2d, istd, x3d = prep(coords_2d), prep(coords_2d_istd), prep(coords_3d)
+    assert x2d.shape == (B, P, 2) and istd.shape == (B, P, 2) and x3d.shape == (B, P, 3)
+    conv = lambda t, dtype, *shape: t.detach().to(device=dev, dtype=dtype).reshape(*shape).contiguous() if t is not None else None
+    cam, ur, vr = conv(cam_mats, torch.float32, -1, 3, 3), conv(u_range, torch.float32, -1, 2), conv(v_range, torch.float32, -1, 2)
+    keep = dict(x2d=x2d, istd=istd, x3d=x3d, cam_mats=cam, u_range=ur, v_range=vr, ransac_thr=conv(ransac_thr, torch.float32, -1),
+                init_pose=conv(init_pose, torch.float64, -1, 4))
+    common = dict(x2d=x2d.data_ptr(), x2d_strides=_strides(x2d), istd=istd.data_ptr(), istd_strides=_strides(istd), x3d=x3d.data_ptr(),
+                  x3d_strides=_strides(x3d), in_dtype=_DTYPES[x2d.dtype], cam_mats=cam.data_ptr(), cam_batch=cam.shape[0])
+    if ur is not None:
+        assert ur.shape[0] == vr.shape[0]
+        common.update(u_range=ur.data_ptr(), v_range=vr.data_ptr(), range_batch=ur.shape[0])
+    return dev, B, P, common, keep
+
+
+def _outputs(dev, B, P, with_diag, out=None, mask=None):
+    """(valid u8 (B,), pose f32 (B,4), cov f32 (B,4,4), tr f32 (B,), mask u8 (B,P), diag f32 (B,4) | None) and the same as arguments under
+    the header's names.  New tensors, or the valid / pose / cov / tr of `out` and the caller's `mask` buffer."""
+    f32 = dict(device=dev, dtype=torch.float32)
+    if out is None:
+        valid, pose, cov, tr = torch.empty(B, device=dev, dtype=torch.uint8), torch.empty(B, 4, **f32), torch.empty(B, 4, 4, **f32), torch.empty(B, **f32)
+    else:                                       # e.g. the typed views of parallel.PackedResults
+        valid, pose, cov, tr = out.valid, out.pose, out.cov, out.tr
+    if mask is None:
+        mask = torch.empty(B, P, device=dev, dtype=torch.uint8)
+    assert mask.shape == (B, P) and mask.dtype == torch.uint8 and mask.is_contiguous()
+    diag = torch.empty(B, 4, **f32) if with_diag else None
+    return (valid, pose, cov, tr, mask, diag), dict(valid=valid.data_ptr(), pose=pose.data_ptr(), cov=cov.data_ptr(), tr_radius=tr.data_ptr(),
+                                                    inlier_mask=mask.data_ptr(), diag=_lib.ptr(diag))
+
+
+def _init_buffers(dev, B, P):
+    """What the initialiser hands to the LM launch: (init_pose f64 (B,4) [yaw0, t], init_mask u8 (B,P), init_valid u8 (B,))."""
+    return (torch.empty(B, 4, device=dev, dtype=torch.float64), torch.empty(B, P, device=dev, dtype=torch.uint8),
+            torch.empty(B, device=dev, dtype=torch.uint8))
 
 
 def pnp_uncert_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min=0.5,
@@ -33,42 +98,16 @@ def pnp_uncert_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v
     """Launch the fused kernel on CUDA(HIP) tensors; returns raw device outputs
     (valid u8 (B,), pose f32 (B,4), cov f32 (B,4,4), tr f32 (B,), mask u8 (B,P), diag f32 (B,4)|None)."""
     lib = _lib.load()
-    dev = coords_2d.device
-    if dev.type != 'cuda':
-        raise RuntimeError('monorun_amd PnP runs on an MI355X only: inputs must be on a HIP device '
-                           '(there is no CPU fallback)')
-    B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
-    dt = coords_2d.dtype if coords_2d.dtype in _DTYPES else torch.float32
-
-    def prep(t):
-        t = t.detach()
-        return t if (t.dtype == dt and t.device == dev) else t.to(device=dev, dtype=dt)
-    x2d, istd, x3d = prep(coords_2d), prep(coords_2d_istd), prep(coords_3d)
-    assert x2d.shape == (B, P, 2) and istd.shape == (B, P, 2) and x3d.shape == (B, P, 3)
-    f32 = dict(device=dev, dtype=torch.float32)
-    cam = cam_mats.detach().to(**f32).reshape(-1, 3, 3).contiguous()
-    ur = u_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    vr = v_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    assert ur.shape[0] == vr.shape[0]
-    thr = epnp_ransac_thres.detach().to(**f32).reshape(-1).contiguous() if epnp_ransac_thres is not None else None
-    ini = init_pose.detach().to(device=dev, dtype=torch.float64).reshape(-1, 4).contiguous() if init_pose is not None else None
-    valid = torch.empty(B, device=dev, dtype=torch.uint8)
-    pose = torch.empty(B, 4, **f32)
-    cov = torch.empty(B, 4, 4, **f32)
-    tr = torch.empty(B, **f32)
-    mask = torch.empty(B, P, device=dev, dtype=torch.uint8)
-    diag = torch.empty(B, 4, **f32) if with_diag else None
+    dev, B, P, common, keep = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, epnp_ransac_thres, init_pose,
+                                      no_gpu='monorun_amd PnP runs on an MI355X only: inputs must be on a HIP device (there is no CPU fallback)')
+    outs, out_args = _outputs(dev, B, P, with_diag)
     if B > 0:
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _lib.check(lib.mr_pnp_uncert_batched(
-                x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d), _DTYPES[dt],
-                cam.data_ptr(), cam.shape[0], ur.data_ptr(), vr.data_ptr(), ur.shape[0],
-                thr.data_ptr() if thr is not None else None, ini.data_ptr() if ini is not None else None, B, P,
-                float(z_min), float(epnp_istd_thres), int(bool(inlier_opt_only)), int(flags),
-                valid.data_ptr(), pose.data_ptr(), cov.data_ptr(), tr.data_ptr(), mask.data_ptr(),
-                diag.data_ptr() if diag is not None else None, stream))
-    return valid, pose, cov, tr, mask, diag
+            _lib.check(lib.mr_pnp_uncert_batched(*_lib.pack(
+                'mr_pnp_uncert_batched', common, ransac_thr=_lib.ptr(keep['ransac_thr']), init_pose=_lib.ptr(keep['init_pose']), B=B, P=P, z_min=float(z_min),
+                istd_thres=float(epnp_istd_thres), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags), **out_args),
+                torch.cuda.current_stream(dev).cuda_stream))
+    return outs
 
 
 def epnp_ransac_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, epnp_istd_thres=1.0, epnp_ransac_thres=None, flags=0,
@@ -77,33 +116,21 @@ def epnp_ransac_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, epnp_istd
     flags=SOLVEPNP_EPNP) on the istd candidates of every object (plain EPnP without thresholds), pnp_uncert_cpu.py:33-68.
     Returns (init_pose f64 (B,4) [yaw0, t], init_mask u8 (B,P), init_valid u8 (B,), diag f32 (B,4)|None, hypotheses f64 (B,30,12)|None)."""
     lib = _lib.load()
-    dev = coords_2d.device
-    if dev.type != 'cuda':
-        raise RuntimeError('monorun_amd EPnP/RANSAC runs on an MI355X only (no CPU fallback)')
-    if first_round is not None:                       # hypotheses solved for every object before the replayed loop is consulted (1..30; result-neutral)
-        flags = (int(flags) & ~(0x1F << _lib.MR_EPNP_FIRST_ROUND_SHIFT)) | (max(1, min(30, int(first_round))) << _lib.MR_EPNP_FIRST_ROUND_SHIFT)
-    B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
-    dt = coords_2d.dtype if coords_2d.dtype in _DTYPES else torch.float32
-    prep = lambda t: t.detach() if (t.dtype == dt and t.device == dev) else t.detach().to(device=dev, dtype=dt)
-    x2d, istd, x3d = prep(coords_2d), prep(coords_2d_istd), prep(coords_3d)
-    f32 = dict(device=dev, dtype=torch.float32)
-    cam = cam_mats.detach().to(**f32).reshape(-1, 3, 3).contiguous()
-    thr = epnp_ransac_thres.detach().to(**f32).reshape(-1).contiguous() if epnp_ransac_thres is not None else None
-    init_pose = torch.empty(B, 4, device=dev, dtype=torch.float64)
-    init_mask = torch.empty(B, P, device=dev, dtype=torch.uint8)
-    init_valid = torch.empty(B, device=dev, dtype=torch.uint8)
-    diag = torch.empty(B, 4, **f32) if with_diag else None
+    dev, B, P, common, keep = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, ransac_thr=epnp_ransac_thres,
+                                      no_gpu='monorun_amd EPnP/RANSAC runs on an MI355X only (no CPU fallback)')
+    init_pose, init_mask, init_valid = _init_buffers(dev, B, P)
+    diag = torch.empty(B, 4, device=dev, dtype=torch.float32) if with_diag else None
     hyp = torch.zeros(B, 30, 12, device=dev, dtype=torch.float64) if debug_hypotheses else None
     if B > 0:
         with torch.cuda.device(dev):
             # the launches of the call hand their intermediate results over in a workspace: from torch's caching allocator, on the
             # stream the launches go to (the block returns to the allocator when `work` dies; stream order keeps that safe)
             work = torch.empty(int(lib.mr_epnp_workspace_bytes(B, P)), device=dev, dtype=torch.uint8)
-            _lib.check(lib.mr_epnp_ransac_batched(
-                x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d), _DTYPES[dt],
-                cam.data_ptr(), cam.shape[0], thr.data_ptr() if thr is not None else None, B, P, float(epnp_istd_thres), int(flags), int(max_iters),
-                init_pose.data_ptr(), init_mask.data_ptr(), init_valid.data_ptr(), diag.data_ptr() if diag is not None else None,
-                hyp.data_ptr() if hyp is not None else None, work.data_ptr(), work.numel(), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(lib.mr_epnp_ransac_batched(*_lib.pack(
+                'mr_epnp_ransac_batched', common, ransac_thr=_lib.ptr(keep['ransac_thr']), B=B, P=P, istd_thres=float(epnp_istd_thres),
+                flags=_first_round_flags(flags, first_round), max_iters=int(max_iters), init_pose=init_pose.data_ptr(), init_mask=init_mask.data_ptr(),
+                init_valid=init_valid.data_ptr(), diag=_lib.ptr(diag), debug_hypotheses=_lib.ptr(hyp), workspace=work.data_ptr(), workspace_bytes=work.numel()),
+                torch.cuda.current_stream(dev).cuda_stream))
     return init_pose, init_mask, init_valid, diag, hyp
 
 
@@ -112,33 +139,17 @@ def pnp_uncert_from_init_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, 
     """LM + covariance from an external initialiser's (init_pose f64 (B,4), init_mask u8 (B,P), init_valid u8 (B,))
     (``mr_pnp_uncert_from_init_batched``).  Returns what ``pnp_uncert_device`` returns."""
     lib = _lib.load()
-    dev = coords_2d.device
-    B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
-    dt = coords_2d.dtype if coords_2d.dtype in _DTYPES else torch.float32
-    prep = lambda t: t.detach() if (t.dtype == dt and t.device == dev) else t.detach().to(device=dev, dtype=dt)
-    x2d, istd, x3d = prep(coords_2d), prep(coords_2d_istd), prep(coords_3d)
-    f32 = dict(device=dev, dtype=torch.float32)
-    cam = cam_mats.detach().to(**f32).reshape(-1, 3, 3).contiguous()
-    ur = u_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    vr = v_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    ini = init_pose.detach().to(device=dev, dtype=torch.float64).reshape(-1, 4).contiguous()
+    dev, B, P, common, keep = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, init_pose=init_pose)
     im = init_mask.detach().to(device=dev, dtype=torch.uint8).contiguous()
     iv = init_valid.detach().to(device=dev, dtype=torch.uint8).contiguous()
-    valid = torch.empty(B, device=dev, dtype=torch.uint8)
-    pose = torch.empty(B, 4, **f32)
-    cov = torch.empty(B, 4, 4, **f32)
-    tr = torch.empty(B, **f32)
-    mask = torch.empty(B, P, device=dev, dtype=torch.uint8)
-    diag = torch.empty(B, 4, **f32) if with_diag else None
+    outs, out_args = _outputs(dev, B, P, with_diag)
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp_uncert_from_init_batched(
-                x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d), _DTYPES[dt],
-                cam.data_ptr(), cam.shape[0], ur.data_ptr(), vr.data_ptr(), ur.shape[0],
-                ini.data_ptr(), im.data_ptr(), iv.data_ptr(), B, P, float(z_min), int(bool(inlier_opt_only)), int(flags),
-                valid.data_ptr(), pose.data_ptr(), cov.data_ptr(), tr.data_ptr(), mask.data_ptr(),
-                diag.data_ptr() if diag is not None else None, torch.cuda.current_stream(dev).cuda_stream))
-    return valid, pose, cov, tr, mask, diag
+            _lib.check(lib.mr_pnp_uncert_from_init_batched(*_lib.pack(
+                'mr_pnp_uncert_from_init_batched', common, init_pose=keep['init_pose'].data_ptr(), init_mask=im.data_ptr(), init_valid=iv.data_ptr(),
+                B=B, P=P, z_min=float(z_min), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags), **out_args),
+                torch.cuda.current_stream(dev).cuda_stream))
+    return outs
 
 
 def pnp_uncert_epnp_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, z_min=0.5, epnp_istd_thres=1.0,
@@ -148,44 +159,27 @@ def pnp_uncert_epnp_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_ran
     bit for bit, as ``epnp_ransac_device`` followed by ``pnp_uncert_from_init_device``; one launch and one pass over the correspondences
     less.  Returns (valid, pose, cov, tr, mask, diag|None, init_pose f64 (B,4), init_valid u8 (B,))."""
     lib = _lib.load()
-    dev = coords_2d.device
-    if dev.type != 'cuda':
-        raise RuntimeError('monorun_amd EPnP/RANSAC runs on an MI355X only (no CPU fallback)')
-    iflags = int(flags) & 0x1047                   # the bits the initialiser reads: istd mean order, MR_NO_ISTD_MASK, MR_EPNP_REFIT_F32, MR_EPNP_CV_EARLY_RETURN
-    if first_round is not None:
-        iflags |= max(1, min(30, int(first_round))) << _lib.MR_EPNP_FIRST_ROUND_SHIFT
-    B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
-    dt = coords_2d.dtype if coords_2d.dtype in _DTYPES else torch.float32
-    prep = lambda t: t.detach() if (t.dtype == dt and t.device == dev) else t.detach().to(device=dev, dtype=dt)
-    x2d, istd, x3d = prep(coords_2d), prep(coords_2d_istd), prep(coords_3d)
-    f32 = dict(device=dev, dtype=torch.float32)
-    cam = cam_mats.detach().to(**f32).reshape(-1, 3, 3).contiguous()
-    ur = u_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    vr = v_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    thr = epnp_ransac_thres.detach().to(**f32).reshape(-1).contiguous() if epnp_ransac_thres is not None else None
-    init_pose = torch.empty(B, 4, device=dev, dtype=torch.float64)
-    init_mask = torch.empty(B, P, device=dev, dtype=torch.uint8)
-    init_valid = torch.empty(B, device=dev, dtype=torch.uint8)
-    valid = torch.empty(B, device=dev, dtype=torch.uint8)
-    pose = torch.empty(B, 4, **f32)
-    cov = torch.empty(B, 4, 4, **f32)
-    tr = torch.empty(B, **f32)
-    mask = torch.empty(B, P, device=dev, dtype=torch.uint8)
-    diag = torch.empty(B, 4, **f32) if with_diag else None
+    dev, B, P, common, keep = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, epnp_ransac_thres,
+                                      no_gpu='monorun_amd EPnP/RANSAC runs on an MI355X only (no CPU fallback)')
+    init_pose, init_mask, init_valid = _init_buffers(dev, B, P)
+    init_args = dict(init_pose=init_pose.data_ptr(), init_mask=init_mask.data_ptr(), init_valid=init_valid.data_ptr())
+    outs, out_args = _outputs(dev, B, P, with_diag)
     if B > 0:
-        one = lambda t: (ctypes.c_void_p * 1)(t.data_ptr() if t is not None else None)
+        fused = 'mr_pnp_uncert_from_epnp_grouped'
+        lm = dict(common, **init_args, **out_args)
+        tables = {k: (ctypes.c_void_p * 1)(lm[k]) for k in _lib.table_args(fused) if k in lm}          # a launch set of one call
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
             work = torch.empty(int(lib.mr_epnp_workspace_bytes(B, P)), device=dev, dtype=torch.uint8)     # (stream order keeps its reuse safe)
-            head = [x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d), _DTYPES[dt], cam.data_ptr(), cam.shape[0]]
-            _lib.check(lib.mr_epnp_ransac_batched(*head, thr.data_ptr() if thr is not None else None, B, P, float(epnp_istd_thres),
-                                                  iflags | _lib.MR_EPNP_DEFER_REFIT, int(max_iters), init_pose.data_ptr(), init_mask.data_ptr(),
-                                                  init_valid.data_ptr(), None, None, work.data_ptr(), work.numel(), st))
-            _lib.check(lib.mr_pnp_uncert_from_epnp_grouped(
-                1, one(x2d), _strides(x2d), one(istd), _strides(istd), one(x3d), _strides(x3d), _DTYPES[dt], one(cam), cam.shape[0], one(ur), one(vr), ur.shape[0],
-                one(init_pose), one(init_mask), one(init_valid), None, B, P, float(z_min), int(bool(inlier_opt_only)), int(flags),
-                one(valid), one(pose), one(cov), one(tr), one(mask), one(diag), None, 0.0, None, work.data_ptr(), work.numel(), st))
-    return valid, pose, cov, tr, mask, diag, init_pose, init_valid
+            work_args = dict(workspace=work.data_ptr(), workspace_bytes=work.numel())
+            _lib.check(lib.mr_epnp_ransac_batched(*_lib.pack(
+                'mr_epnp_ransac_batched', common, ransac_thr=_lib.ptr(keep['ransac_thr']), B=B, P=P, istd_thres=float(epnp_istd_thres),
+                flags=_first_round_flags(int(flags) & _INIT_FLAGS, first_round) | _lib.MR_EPNP_DEFER_REFIT, max_iters=int(max_iters), **init_args,
+                diag=None, debug_hypotheses=None, **work_args), st))
+            _lib.check(lib.mr_pnp_uncert_from_epnp_grouped(*_lib.pack(
+                fused, common, ncalls=1, **tables, epnp_diag=None, B=B, P=P, z_min=float(z_min), inlier_opt_only=int(bool(inlier_opt_only)),
+                flags=int(flags), cov_calib_logscale=None, cov_corr_sd=0.0, cov_calib=None, **work_args), st))
+    return outs + (init_pose, init_valid)
 
 
 def cov_symeig_rule_device(valid_u8, cov, with_eigs=False):
@@ -197,8 +191,7 @@ def cov_symeig_rule_device(valid_u8, cov, with_eigs=False):
     lam = torch.empty(B, 2, device=cov.device, dtype=torch.float32) if with_eigs else None
     if B > 0:
         with torch.cuda.device(cov.device):
-            _lib.check(lib.mr_cov_symeig_rule(valid_u8.data_ptr(), cov.data_ptr(), B, lam.data_ptr() if lam is not None else None,
-                                              torch.cuda.current_stream(cov.device).cuda_stream))
+            _lib.check(lib.mr_cov_symeig_rule(valid_u8.data_ptr(), cov.data_ptr(), B, _lib.ptr(lam), torch.cuda.current_stream(cov.device).cuda_stream))
     return lam
 
 
@@ -211,36 +204,13 @@ class PnPLaunch:
                  epnp_istd_thres=0.6, epnp_ransac_thres=None, inlier_opt_only=True, init_pose=None, flags=0,
                  out=None, with_diag=False, mask=None):
         self.lib = _lib.load()
-        dev = coords_2d.device
-        if dev.type != 'cuda':
-            raise RuntimeError('PnPLaunch needs HIP device tensors (no CPU fallback)')
-        self.dev = dev
-        B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
-        assert coords_2d.dtype in _DTYPES and coords_2d_istd.dtype == coords_2d.dtype == coords_3d.dtype
-        f32 = dict(device=dev, dtype=torch.float32)
-        self.keep = [coords_2d, coords_2d_istd, coords_3d,
-                     cam_mats.to(**f32).reshape(-1, 3, 3).contiguous(), u_range.to(**f32).reshape(-1, 2).contiguous(),
-                     v_range.to(**f32).reshape(-1, 2).contiguous(),
-                     epnp_ransac_thres.to(**f32).reshape(-1).contiguous() if epnp_ransac_thres is not None else None,
-                     init_pose.to(device=dev, dtype=torch.float64).reshape(-1, 4).contiguous() if init_pose is not None else None]
-        x2d, istd, x3d, cam, ur, vr, thr, ini = self.keep
-        if out is None:
-            self.valid = torch.empty(B, device=dev, dtype=torch.uint8)
-            self.pose = torch.empty(B, 4, **f32)
-            self.cov = torch.empty(B, 4, 4, **f32)
-            self.tr = torch.empty(B, **f32)
-        else:                                   # e.g. the typed views of parallel.PackedResults
-            self.valid, self.pose, self.cov, self.tr = out.valid, out.pose, out.cov, out.tr
-        self.mask = mask if mask is not None else torch.empty(B, P, device=dev, dtype=torch.uint8)
-        assert self.mask.shape == (B, P) and self.mask.dtype == torch.uint8 and self.mask.is_contiguous()
-        self.diag = torch.empty(B, 4, **f32) if with_diag else None
+        self.dev, B, P, common, self.keep = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, epnp_ransac_thres, init_pose,
+                                                    no_gpu='PnPLaunch needs HIP device tensors (no CPU fallback)', prepared=True)
+        (self.valid, self.pose, self.cov, self.tr, self.mask, self.diag), out_args = _outputs(self.dev, B, P, with_diag, out, mask)
         self.B = B
-        self.args = [x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d),
-                     _DTYPES[x2d.dtype], cam.data_ptr(), cam.shape[0], ur.data_ptr(), vr.data_ptr(), ur.shape[0],
-                     thr.data_ptr() if thr is not None else None, ini.data_ptr() if ini is not None else None, B, P,
-                     float(z_min), float(epnp_istd_thres), int(bool(inlier_opt_only)), int(flags),
-                     self.valid.data_ptr(), self.pose.data_ptr(), self.cov.data_ptr(), self.tr.data_ptr(),
-                     self.mask.data_ptr(), self.diag.data_ptr() if self.diag is not None else None]
+        self.named = dict(common, ransac_thr=_lib.ptr(self.keep['ransac_thr']), init_pose=_lib.ptr(self.keep['init_pose']), B=B, P=P, z_min=float(z_min),
+                          istd_thres=float(epnp_istd_thres), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags), **out_args)
+        self.args = _lib.pack('mr_pnp_uncert_batched', self.named)
 
     def run(self, stream=None):
         if self.B == 0:
@@ -278,43 +248,25 @@ class PnPEpnpLaunch:
         buffer; work: a uint8 workspace of at least mr_epnp_workspace_bytes(B, P) bytes that SEVERAL launches may share when they
         only ever run on one stream (stream order keeps that safe).  All three default to tensors of the launch's own."""
         self.lib = lib = _lib.load()
-        dev = coords_2d.device
-        if dev.type != 'cuda':
-            raise RuntimeError('PnPEpnpLaunch needs HIP device tensors (no CPU fallback)')
-        self.dev = dev
-        B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
-        assert coords_2d.dtype in _DTYPES and coords_2d_istd.dtype == coords_2d.dtype == coords_3d.dtype
-        f32 = dict(device=dev, dtype=torch.float32)
-        self.keep = [coords_2d, coords_2d_istd, coords_3d,
-                     cam_mats.to(**f32).reshape(-1, 3, 3).contiguous(), u_range.to(**f32).reshape(-1, 2).contiguous(),
-                     v_range.to(**f32).reshape(-1, 2).contiguous(),
-                     epnp_ransac_thres.to(**f32).reshape(-1).contiguous() if epnp_ransac_thres is not None else None]
-        x2d, istd, x3d, cam, ur, vr, thr = self.keep
-        self.init_pose = torch.empty(B, 4, device=dev, dtype=torch.float64)
-        self.init_mask = torch.empty(B, P, device=dev, dtype=torch.uint8)
-        self.init_valid = torch.empty(B, device=dev, dtype=torch.uint8)
-        self.init_diag = torch.empty(B, 4, **f32) if with_diag else None
+        self.dev, B, P, common, self.keep = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, epnp_ransac_thres,
+                                                    no_gpu='PnPEpnpLaunch needs HIP device tensors (no CPU fallback)', prepared=True)
+        dev = self.dev
+        self.init_pose, self.init_mask, self.init_valid = _init_buffers(dev, B, P)
+        self.init_diag = torch.empty(B, 4, device=dev, dtype=torch.float32) if with_diag else None
         need = int(lib.mr_epnp_workspace_bytes(B, P)) if B > 0 else 0
         self.work = work if work is not None else torch.empty(need, device=dev, dtype=torch.uint8)
         assert self.work.dtype == torch.uint8 and self.work.numel() >= need and self.work.data_ptr() % 256 == 0
-        if out is None:
-            self.valid = torch.empty(B, device=dev, dtype=torch.uint8)
-            self.pose = torch.empty(B, 4, **f32)
-            self.cov = torch.empty(B, 4, 4, **f32)
-            self.tr = torch.empty(B, **f32)
-        else:
-            self.valid, self.pose, self.cov, self.tr = out.valid, out.pose, out.cov, out.tr
-        self.mask = mask if mask is not None else torch.empty(B, P, device=dev, dtype=torch.uint8)
-        assert self.mask.shape == (B, P) and self.mask.dtype == torch.uint8 and self.mask.is_contiguous()
-        self.diag = torch.empty(B, 4, **f32) if with_diag else None
+        (self.valid, self.pose, self.cov, self.tr, self.mask, self.diag), out_args = _outputs(dev, B, P, with_diag, out, mask)
         self.B = B
-        head = [x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d), _DTYPES[x2d.dtype], cam.data_ptr(), cam.shape[0]]
-        self.args_init = head + [thr.data_ptr() if thr is not None else None, B, P, float(epnp_istd_thres), (int(flags) & 0x1047) | ((max(1, min(30, int(first_round))) << _lib.MR_EPNP_FIRST_ROUND_SHIFT) if first_round is not None else 0),
-                                 int(max_iters), self.init_pose.data_ptr(), self.init_mask.data_ptr(), self.init_valid.data_ptr(),
-                                 self.init_diag.data_ptr() if self.init_diag is not None else None, None, self.work.data_ptr(), self.work.numel()]
-        self.args_lm = head + [ur.data_ptr(), vr.data_ptr(), ur.shape[0], self.init_pose.data_ptr(), self.init_mask.data_ptr(), self.init_valid.data_ptr(),
-                               B, P, float(z_min), int(bool(inlier_opt_only)), int(flags), self.valid.data_ptr(), self.pose.data_ptr(), self.cov.data_ptr(),
-                               self.tr.data_ptr(), self.mask.data_ptr(), self.diag.data_ptr() if self.diag is not None else None]
+        init_args = dict(init_pose=self.init_pose.data_ptr(), init_mask=self.init_mask.data_ptr(), init_valid=self.init_valid.data_ptr())
+        # the arguments of the two entry points by the header's names, on top of the common ones: what a launch set reads of its members
+        # (plain numbers and ctypes arrays: nothing in them refers to this object)
+        self.named_init = dict(common, ransac_thr=_lib.ptr(self.keep['ransac_thr']), B=B, P=P, istd_thres=float(epnp_istd_thres),
+                               flags=_first_round_flags(int(flags) & _INIT_FLAGS, first_round), max_iters=int(max_iters), **init_args,
+                               diag=_lib.ptr(self.init_diag), debug_hypotheses=None, workspace=self.work.data_ptr(), workspace_bytes=self.work.numel())
+        self.named_lm = dict(common, **init_args, B=B, P=P, z_min=float(z_min), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags), **out_args)
+        self.args_init = _lib.pack('mr_epnp_ransac_batched', self.named_init)
+        self.args_lm = _lib.pack('mr_pnp_uncert_from_init_batched', self.named_lm)
         self.calib = calib
         if calib is not None:
             ls, _, co = calib
@@ -343,6 +295,28 @@ class PnPEpnpLaunch:
             _lib.check(code)
 
 
+# what the members of a launch set must agree in, by argument name: (equal values, pointers given or left out together), for the
+# initialiser (mr_epnp_ransac_batched) and for the LM launch (mr_pnp_uncert_from_init_batched)
+_SET_INIT = (('x2d_strides', 'istd_strides', 'x3d_strides', 'in_dtype', 'cam_batch', 'B', 'P', 'istd_thres', 'flags', 'max_iters'), ('ransac_thr', 'diag'))
+_SET_LM = (('range_batch', 'z_min', 'inlier_opt_only', 'flags'), ('diag',))
+
+
+def _require_agreement(members, rule, what):
+    """ValueError unless the named arguments of every member agree with the first's under `rule` (_SET_INIT / _SET_LM)."""
+    equal, together = rule
+    val = lambda v: tuple(v) if isinstance(v, ctypes.Array) else v
+    for m in members[1:]:
+        if any(val(m[k]) != val(members[0][k]) for k in equal) or any((m[k] is None) != (members[0][k] is None) for k in together):
+            raise ValueError(f'the members of a group must share {what}')
+
+
+def _tables(fn, members, **per_member):
+    """{name: (void *)[n] of the members' pointers} for every argument `fn` declares as a per-call pointer table; the pointers of a
+    name come from `per_member` (a list) where it is given, else from the members' named arguments."""
+    n = len(members)
+    return {k: (ctypes.c_void_p * n)(*(per_member[k] if k in per_member else [m[k] for m in members])) for k in _lib.table_args(fn)}
+
+
 class PnPEpnpGroupLaunch:
     """Up to eight prepared ``PnPEpnpLaunch`` objects of the same shape whose initialisers run as ONE launch set
     (``mr_epnp_ransac_grouped``: every launch of csrc/epnp_stages.inc carries the objects of all members), followed by each
@@ -366,47 +340,36 @@ class PnPEpnpGroupLaunch:
             raise ValueError('PnPEpnpGroupLaunch takes 1 to 8 launches')
         f = self.members[0]
         self.lib, self.dev, self.B = f.lib, f.dev, f.B
-        ai = f.args_init
-        same = lambda m: (m.B == f.B and m.dev == f.dev and tuple(m.args_init[1]) == tuple(ai[1]) and tuple(m.args_init[3]) == tuple(ai[3]) and
-                          tuple(m.args_init[5]) == tuple(ai[5]) and m.args_init[6] == ai[6] and m.args_init[8] == ai[8] and m.args_init[11:15] == ai[11:15] and
-                          (m.args_init[9] is None) == (ai[9] is None) and (m.args_init[18] is None) == (ai[18] is None))
-        if not all(same(m) for m in self.members):
-            raise ValueError('the members of a group must share shape, strides, dtype, camera batching, thresholds and flags')
-        arr = lambda k: (ctypes.c_void_p * n)(*[m.args_init[k] for m in self.members])
-        self._arrays = [arr(k) for k in (0, 2, 4, 7, 9, 15, 16, 17, 18)]
-        x2d, istd, x3d, cam, thr, ipose, imask, ivalid, idiag = self._arrays
-        P = ai[11]
-        need = int(self.lib.mr_epnp_workspace_bytes(n * f.B, P)) if f.B > 0 else 0
+        inits, lms = [m.named_init for m in self.members], [m.named_lm for m in self.members]
+        what = 'shape, strides, dtype, camera batching, thresholds and flags'
+        if any(m.dev != f.dev for m in self.members):
+            raise ValueError(f'the members of a group must share {what}')
+        _require_agreement(inits, _SET_INIT, what)
+        need = int(self.lib.mr_epnp_workspace_bytes(n * f.B, inits[0]['P'])) if f.B > 0 else 0
         self.work = work if work is not None else torch.empty(need, device=f.dev, dtype=torch.uint8)
         assert self.work.dtype == torch.uint8 and self.work.numel() >= need and self.work.data_ptr() % 256 == 0
         if lm not in ('fused', 'grouped', 'side_by_side', 'serial'):
             raise ValueError("lm must be 'fused', 'grouped', 'side_by_side' or 'serial'")
-        self.args = [n, x2d, ai[1], istd, ai[3], x3d, ai[5], ai[6], cam, ai[8], thr, f.B, P, ai[12],
-                     int(ai[13]) | (_lib.MR_EPNP_DEFER_REFIT if lm == 'fused' else 0), ai[14],
-                     ipose, imask, ivalid, idiag, self.work.data_ptr(), self.work.numel()]
-        al = f.args_lm
-        lm_same = lambda m: (m.args_lm[11] == al[11] and m.args_lm[17:20] == al[17:20] and (m.args_lm[25] is None) == (al[25] is None))
-        if not all(lm_same(m) for m in self.members):
-            raise ValueError('the members of a group must share range batching, z_min, inlier_opt_only and flags')
+        work_args = dict(workspace=self.work.data_ptr(), workspace_bytes=self.work.numel())
+        self.args = _lib.pack('mr_epnp_ransac_grouped', inits[0], ncalls=n, **_tables('mr_epnp_ransac_grouped', inits),
+                              flags=inits[0]['flags'] | (_lib.MR_EPNP_DEFER_REFIT if lm == 'fused' else 0), **work_args)
+        _require_agreement(lms, _SET_LM, 'range batching, z_min, inlier_opt_only and flags')
         self.lm = lm
-        larr = lambda k: (ctypes.c_void_p * n)(*[m.args_lm[k] for m in self.members])
-        self._lm_arrays = {k: larr(k) for k in (9, 10, 12, 13, 14, 20, 21, 22, 23, 24, 25)}
-        la = self._lm_arrays
-        self.args_lm = [n, x2d, al[1], istd, al[3], x3d, al[5], al[6], cam, al[8], la[9], la[10], al[11], la[12], la[13], la[14], f.B, P, al[17], al[18], al[19],
-                        la[20], la[21], la[22], la[23], la[24], la[25]]
         cal = [getattr(m, 'calib', None) for m in self.members]
         if any(c is not None for c in cal) and (any(c is None for c in cal) or any(c[0].data_ptr() != cal[0][0].data_ptr() or c[1] != cal[0][1] for c in cal)):
             raise ValueError('the members of a group must share the calibration (log-scale tensor and distance constant), or have none')
         if cal[0] is not None and lm != 'fused':
             raise ValueError("calibrated covariances are written by the 'fused' form")
-        self._calib_arr = (ctypes.c_void_p * n)(*[c[2].data_ptr() for c in cal]) if cal[0] is not None else None
-        self.args_fused = self.args_lm[:16] + [idiag] + self.args_lm[16:] + [cal[0][0].data_ptr() if cal[0] is not None else None, float(cal[0][1]) if cal[0] is not None else 0.0,
-                                                                             self._calib_arr, self.work.data_ptr(), self.work.numel()]
-        self._lm_any = []
-        for m in self.members:                             # args_lm with MR_ANY_ORDER in its flags (argument 19 of mr_pnp_uncert_from_init_batched)
-            a = list(m.args_lm)
-            a[19] = int(a[19]) | _lib.MR_ANY_ORDER
-            self._lm_any.append(a)
+        # the tables of the LM launch over the set, with the re-fit in it (the one behind the complete initialiser takes a part of them)
+        tables = _tables('mr_pnp_uncert_from_epnp_grouped', lms, epnp_diag=[i['diag'] for i in inits],
+                         cov_calib=[c[2].data_ptr() if c is not None else None for c in cal])
+        if cal[0] is None:
+            tables['cov_calib'] = None
+        self.args_lm = _lib.pack('mr_pnp_uncert_from_init_grouped', dict(lms[0], **tables), ncalls=n)
+        self.args_fused = _lib.pack('mr_pnp_uncert_from_epnp_grouped', lms[0], ncalls=n, **tables, cov_calib_logscale=cal[0][0].data_ptr() if cal[0] is not None else None,
+                                    cov_corr_sd=float(cal[0][1]) if cal[0] is not None else 0.0, **work_args)
+        # 'side_by_side': the members' own LM launches with MR_ANY_ORDER in their flags
+        self._lm_any = [_lib.pack('mr_pnp_uncert_from_init_batched', l, flags=l['flags'] | _lib.MR_ANY_ORDER) for l in lms] if lm == 'side_by_side' else None
 
     def run(self, stream=None):
         if self.B == 0:
@@ -547,26 +510,18 @@ def pnp6_refine_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, 
     """Second launch of the 6-DoF mode (``mr_pnp6_refine_batched``): 6-DoF LM from the 4-DoF result on its inlier set.
     Returns (valid u8 (B,), pose6 f32 (B,6) [rx,ry,rz,tx,ty,tz], cov6 f32 (B,6,6), diag f32 (B,2)|None)."""
     lib = _lib.load()
-    dev = coords_2d.device
-    B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
-    dt = coords_2d.dtype if coords_2d.dtype in _DTYPES else torch.float32
-    prep = lambda t: t.detach() if (t.dtype == dt and t.device == dev) else t.detach().to(device=dev, dtype=dt)
-    x2d, istd, x3d = prep(coords_2d), prep(coords_2d_istd), prep(coords_3d)
+    dev, B, P, common, _ = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range)
     f32 = dict(device=dev, dtype=torch.float32)
-    cam = cam_mats.detach().to(**f32).reshape(-1, 3, 3).contiguous()
-    ur = u_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    vr = v_range.detach().to(**f32).reshape(-1, 2).contiguous()
+    mask, pose4, valid4 = inlier_mask_u8.contiguous(), pose4.contiguous(), valid4_u8.contiguous()
     valid = torch.empty(B, device=dev, dtype=torch.uint8)
     pose6 = torch.empty(B, 6, **f32)
     cov6 = torch.empty(B, 6, 6, **f32)
     diag = torch.empty(B, 2, **f32) if with_diag else None
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp6_refine_batched(
-                x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d), _DTYPES[dt],
-                cam.data_ptr(), cam.shape[0], ur.data_ptr(), vr.data_ptr(), ur.shape[0],
-                inlier_mask_u8.contiguous().data_ptr(), pose4.contiguous().data_ptr(), valid4_u8.contiguous().data_ptr(), B, P, float(z_min), int(flags),
-                valid.data_ptr(), pose6.data_ptr(), cov6.data_ptr(), diag.data_ptr() if diag is not None else None,
+            _lib.check(lib.mr_pnp6_refine_batched(*_lib.pack(
+                'mr_pnp6_refine_batched', common, inlier_mask=mask.data_ptr(), pose4=pose4.data_ptr(), valid4=valid4.data_ptr(), B=B, P=P,
+                z_min=float(z_min), flags=int(flags), valid=valid.data_ptr(), pose6=pose6.data_ptr(), cov6=cov6.data_ptr(), diag=_lib.ptr(diag)),
                 torch.cuda.current_stream(dev).cuda_stream))
     return valid, pose6, cov6, diag
 
@@ -577,15 +532,8 @@ def exact_hessian_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range
     the masked cost at pose4 (B,4) f32 and its inverse.  inlier_mask_u8 (B,P) u8 | None, valid_u8 (B,) u8 = the 4-DoF solve's flags.
     Returns (valid u8 (B,), cov f32 (B,4,4), hess f32 (B,4,4) | None)."""
     lib = _lib.load()
-    dev = coords_2d.device
-    B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
-    dt = coords_2d.dtype if coords_2d.dtype in _DTYPES else torch.float32
-    prep = lambda t: t.detach() if (t.dtype == dt and t.device == dev) else t.detach().to(device=dev, dtype=dt)
-    x2d, istd, x3d = prep(coords_2d), prep(coords_2d_istd), prep(coords_3d)
+    dev, B, P, common, _ = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range)
     f32 = dict(device=dev, dtype=torch.float32)
-    cam = cam_mats.detach().to(**f32).reshape(-1, 3, 3).contiguous()
-    ur = u_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    vr = v_range.detach().to(**f32).reshape(-1, 2).contiguous()
     valid = valid_u8.detach().to(device=dev, dtype=torch.uint8).clone().contiguous()
     pose = pose4.detach().to(**f32).contiguous()
     mask = inlier_mask_u8.detach().to(device=dev, dtype=torch.uint8).contiguous() if inlier_mask_u8 is not None else None
@@ -593,11 +541,9 @@ def exact_hessian_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range
     hess = torch.empty(B, 4, 4, **f32) if with_hessian else None
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp_exact_hessian_batched(
-                x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d), _DTYPES[dt],
-                cam.data_ptr(), cam.shape[0], ur.data_ptr(), vr.data_ptr(), ur.shape[0],
-                pose.data_ptr(), mask.data_ptr() if mask is not None else None, B, P, float(z_min),
-                valid.data_ptr(), hess.data_ptr() if hess is not None else None, cov.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(lib.mr_pnp_exact_hessian_batched(*_lib.pack(
+                'mr_pnp_exact_hessian_batched', common, pose=pose.data_ptr(), inlier_mask=_lib.ptr(mask), B=B, P=P, z_min=float(z_min),
+                valid=valid.data_ptr(), hess=_lib.ptr(hess), cov=cov.data_ptr()), torch.cuda.current_stream(dev).cuda_stream))
     return valid, cov, hess
 
 
@@ -609,38 +555,25 @@ def pnp_uncert_backward_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u
     lm_all_points: the LM refined every point (inlier_opt_only=False).  needs: which of (x2d, istd, x3d) to compute.
     Returns (grad_x2d f32 (B,P,2) | None, grad_istd f32 (B,P,2) | None, grad_x3d f32 (B,P,3) | None, status u8 (B,) | None)."""
     lib = _lib.load()
-    dev = coords_2d.device
-    if dev.type != 'cuda':
-        raise RuntimeError('monorun_amd PnP backward runs on an MI355X only (no CPU fallback)')
+    dev, B, P, common, _ = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range,
+                                   no_gpu='monorun_amd PnP backward runs on an MI355X only (no CPU fallback)')
     if (cov is None) != (grad_cov is None):
         raise ValueError('cov and grad_cov go together')
-    B, P = int(coords_2d.shape[0]), int(coords_2d.shape[1])
-    dt = coords_2d.dtype if coords_2d.dtype in _DTYPES else torch.float32
-    prep = lambda t: t.detach() if (t.dtype == dt and t.device == dev) else t.detach().to(device=dev, dtype=dt)
-    x2d, istd, x3d = prep(coords_2d), prep(coords_2d_istd), prep(coords_3d)
-    assert x2d.shape == (B, P, 2) and istd.shape == (B, P, 2) and x3d.shape == (B, P, 3)
     f32 = dict(device=dev, dtype=torch.float32)
-    cam = cam_mats.detach().to(**f32).reshape(-1, 3, 3).contiguous()
-    ur = u_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    vr = v_range.detach().to(**f32).reshape(-1, 2).contiguous()
-    pose = pose4.detach().to(**f32).reshape(B, 4).contiguous()
+    conv = lambda t, *shape: t.detach().to(**f32).reshape(*shape).contiguous() if t is not None else None
+    pose, gp, c, gc = conv(pose4, B, 4), conv(grad_pose, B, 4), conv(cov, B, 16), conv(grad_cov, B, 16)
     mask = inlier_mask_u8.detach().to(device=dev, dtype=torch.uint8).contiguous() if inlier_mask_u8 is not None else None
     valid = valid_u8.detach().to(device=dev, dtype=torch.uint8).contiguous()
-    gp = grad_pose.detach().to(**f32).reshape(B, 4).contiguous() if grad_pose is not None else None
-    c = cov.detach().to(**f32).reshape(B, 16).contiguous() if cov is not None else None
-    gc = grad_cov.detach().to(**f32).reshape(B, 16).contiguous() if grad_cov is not None else None
     g2 = torch.empty(B, P, 2, **f32) if needs[0] else None
     gw = torch.empty(B, P, 2, **f32) if needs[1] else None
     g3 = torch.empty(B, P, 3, **f32) if needs[2] else None
     status = torch.empty(B, device=dev, dtype=torch.uint8) if with_status else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp_uncert_backward_batched(
-                x2d.data_ptr(), _strides(x2d), istd.data_ptr(), _strides(istd), x3d.data_ptr(), _strides(x3d), _DTYPES[dt],
-                cam.data_ptr(), cam.shape[0], ur.data_ptr(), vr.data_ptr(), ur.shape[0],
-                pose.data_ptr(), ptr(mask), valid.data_ptr(), int(bool(lm_all_points)), ptr(gp), ptr(c), ptr(gc), B, P, float(z_min),
-                ptr(g2), ptr(gw), ptr(g3), ptr(status), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(lib.mr_pnp_uncert_backward_batched(*_lib.pack(
+                'mr_pnp_uncert_backward_batched', common, pose=pose.data_ptr(), inlier_mask=_lib.ptr(mask), valid=valid.data_ptr(),
+                lm_all_points=int(bool(lm_all_points)), grad_pose=_lib.ptr(gp), cov=_lib.ptr(c), grad_cov=_lib.ptr(gc), B=B, P=P, z_min=float(z_min),
+                grad_x2d=_lib.ptr(g2), grad_istd=_lib.ptr(gw), grad_x3d=_lib.ptr(g3), status=_lib.ptr(status)), torch.cuda.current_stream(dev).cuda_stream))
     return g2, gw, g3, status
 
 

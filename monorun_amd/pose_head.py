@@ -112,13 +112,11 @@ def _coord_map(coord_2d, dev):
     return m.contiguous()
 
 
-def _coord_map_args(coord_2d, dev):
-    """(pointer, H, W) of the optional coord_2d map for ONE launch that is enqueued right after this returns: a converted copy
-    may then be released at once (the caching allocator is stream-ordered).  A prepared launch must hold `_coord_map`'s tensor."""
-    m = _coord_map(coord_2d, dev)
-    if m is None:
-        return None, 0, 0
-    return m.data_ptr(), int(m.shape[1]), int(m.shape[2])
+def _coord_map_args(m):
+    """The coord_2d_map / map_h / map_w arguments of the kernels for `_coord_map`'s tensor (None: no map).  For ONE launch that is
+    enqueued right away a converted copy may be released at once (the caching allocator is stream-ordered); a prepared launch must
+    hold the tensor."""
+    return dict(coord_2d_map=_lib.ptr(m), map_h=int(m.shape[1]) if m is not None else 0, map_w=int(m.shape[2]) if m is not None else 0)
 
 
 def gen_coord_2d(h, w, pad_to=32, flip=False, scale=None, device=None):
@@ -186,6 +184,20 @@ def roi_align_avg(input, rois, output_size, spatial_scale=1.0, sampling_ratio=0,
     return out
 
 
+def _decode_args(all_pred, pred_dtype, labels, flip, dim, dim_var, rois, num_classes, class_agnostic, consts, ref_length, ref_focal_y, target_std,
+                 epistemic_std_gain, std_scale, epnp_ransac_thres_ratio):
+    """The arguments ``mr_noc_decode_batched`` and ``mr_pnp_from_head_batched`` share (the decode: their first 21), by the header's names.
+    consts = the (dim_means, dim_stds, noc_means, noc_stds) device tensors."""
+    B, _, h, w = all_pred.shape
+    mu, sd, nm, ns = consts
+    return dict(all_pred=all_pred.data_ptr(), pred_dtype=pred_dtype, labels=labels.data_ptr(), flip=flip.data_ptr(), dim=dim.data_ptr(),
+                dim_var=_lib.ptr(dim_var), rois=rois.data_ptr(), B=B, num_classes=num_classes,
+                class_agnostic=int(class_agnostic), h=h, w=w, dim_means=mu.data_ptr(), dim_stds=sd.data_ptr(), noc_means=nm.data_ptr(),
+                noc_stds=ns.data_ptr(), proj_scaling_denominator=float(ref_length * ref_focal_y * target_std), ref_focal_y=float(ref_focal_y),
+                epistemic_std_gain=float(epistemic_std_gain), std_scale=float(std_scale),
+                ransac_thres_ratio=float(epnp_ransac_thres_ratio) if epnp_ransac_thres_ratio is not None else -1.0)
+
+
 def noc_decode(all_pred, labels, flip, dim, dim_var, rois, num_classes=3, class_agnostic=False,
                dim_means=DIM_MEANS, dim_stds=DIM_STDS, noc_means=NOC_MEANS, noc_stds=NOC_STDS,
                ref_length=1.6, ref_focal_y=722, target_std=0.15, epistemic_std_gain=1.0,
@@ -224,14 +236,11 @@ def noc_decode(all_pred, labels, flip, dim, dim_var, rois, num_classes=3, class_
     thr = torch.empty(B, **f32) if epnp_ransac_thres_ratio is not None else None
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_noc_decode_batched(
-                ap.data_ptr(), ap_dt, lab.data_ptr(), fl.data_ptr(), dm.data_ptr(), dv.data_ptr() if dv is not None else None, r.data_ptr(),
-                B, num_classes, int(class_agnostic), h, w, mu.data_ptr(), sd.data_ptr(), nm.data_ptr(), ns.data_ptr(),
-                float(ref_length * ref_focal_y * target_std), float(ref_focal_y), float(epistemic_std_gain), float(std_scale),
-                float(epnp_ransac_thres_ratio) if epnp_ransac_thres_ratio is not None else -1.0,
-                c2d.data_ptr(), istd.data_ptr(), c3d.data_ptr(), dims.data_ptr(),
-                dims_var.data_ptr() if dims_var is not None else None, thr.data_ptr() if thr is not None else None,
-                *_coord_map_args(coord_2d, dev), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(lib.mr_noc_decode_batched(*_lib.pack(
+                'mr_noc_decode_batched', **_decode_args(ap, ap_dt, lab, fl, dm, dv, r, num_classes, class_agnostic, (mu, sd, nm, ns), ref_length, ref_focal_y,
+                                                        target_std, epistemic_std_gain, std_scale, epnp_ransac_thres_ratio),
+                coords_2d=c2d.data_ptr(), coords_2d_istd=istd.data_ptr(), coords_3d=c3d.data_ptr(), dims=dims.data_ptr(), dims_var=_lib.ptr(dims_var),
+                ransac_thr=_lib.ptr(thr), **_coord_map_args(_coord_map(coord_2d, dev))), torch.cuda.current_stream(dev).cuda_stream))
     return dict(coords_2d=c2d, coords_2d_istd=istd, coords_3d=c3d, dims=dims, dims_var=dims_var, ransac_thr=thr)
 
 
@@ -268,14 +277,11 @@ class NocDecodeLaunch:
                         ransac_thr=torch.empty(B, **f32) if epnp_ransac_thres_ratio is not None else None)
         o = self.out
         self.B = B
-        self.args = [ap.data_ptr(), ap_dt, i['labels'].data_ptr(), i['flip'].data_ptr(), i['dim'].data_ptr(),
-                     i['dim_var'].data_ptr() if i['dim_var'] is not None else None, r.data_ptr(),
-                     B, num_classes, int(class_agnostic), h, w, mu.data_ptr(), sd.data_ptr(), nm.data_ptr(), ns.data_ptr(),
-                     float(ref_length * ref_focal_y * target_std), float(ref_focal_y), float(epistemic_std_gain), float(std_scale),
-                     float(epnp_ransac_thres_ratio) if epnp_ransac_thres_ratio is not None else -1.0,
-                     o['coords_2d'].data_ptr(), o['coords_2d_istd'].data_ptr(), o['coords_3d'].data_ptr(), o['dims'].data_ptr(),
-                     o['dims_var'].data_ptr() if o['dims_var'] is not None else None, o['ransac_thr'].data_ptr() if o['ransac_thr'] is not None else None,
-                     cmap.data_ptr() if cmap is not None else None, int(cmap.shape[1]) if cmap is not None else 0, int(cmap.shape[2]) if cmap is not None else 0]
+        self.args = _lib.pack(
+            'mr_noc_decode_batched', **_decode_args(ap, ap_dt, i['labels'], i['flip'], i['dim'], i['dim_var'], r, num_classes, class_agnostic, self._keep, ref_length,
+                                                    ref_focal_y, target_std, epistemic_std_gain, std_scale, epnp_ransac_thres_ratio),
+            coords_2d=o['coords_2d'].data_ptr(), coords_2d_istd=o['coords_2d_istd'].data_ptr(), coords_3d=o['coords_3d'].data_ptr(), dims=o['dims'].data_ptr(),
+            dims_var=_lib.ptr(o['dims_var']), ransac_thr=_lib.ptr(o['ransac_thr']), **_coord_map_args(cmap))
 
     def run(self, stream=None):
         if self.B:
@@ -338,20 +344,15 @@ def pnp_from_head(all_pred, labels, flip, dim, dim_var, rois, cam_intrinsic, img
     valid, mask = bbuf[:B], bbuf[B:B + B * P].view(B, P)
     ls = prep(cov_calib_logscale) if calib else None
     if B > 0:
-        mp, mh, mw = _coord_map_args(coord_2d, dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp_from_head_batched(
-                ap.data_ptr(), ap_dt, lab.data_ptr(), fl.data_ptr(), dm.data_ptr(), dv.data_ptr() if dv is not None else None, r.data_ptr(),
-                B, num_classes, int(class_agnostic), h, w, mu.data_ptr(), sd.data_ptr(), nm.data_ptr(), ns.data_ptr(),
-                float(ref_length * ref_focal_y * target_std), float(ref_focal_y), float(epistemic_std_gain), float(std_scale),
-                float(epnp_ransac_thres_ratio) if epnp_ransac_thres_ratio is not None else -1.0,
-                cam.data_ptr(), cam.shape[0], ur.data_ptr(), vr.data_ptr(), ur.shape[0],
-                float(z_min), float(epnp_istd_thres), int(bool(inlier_opt_only)), int(flags),
-                valid.data_ptr(), pose.data_ptr(), cov.data_ptr(), tr.data_ptr(), mask.data_ptr(),
-                diag.data_ptr() if diag is not None else None, dims.data_ptr(),
-                dims_var.data_ptr() if dims_var is not None else None, mp, mh, mw,
-                ls.data_ptr() if calib else None, float(cov_correction_sd), cov_calib.data_ptr() if calib else None,
-                torch.cuda.current_stream(dev).cuda_stream))
+            _lib.check(lib.mr_pnp_from_head_batched(*_lib.pack(
+                'mr_pnp_from_head_batched', **_decode_args(ap, ap_dt, lab, fl, dm, dv, r, num_classes, class_agnostic, (mu, sd, nm, ns), ref_length, ref_focal_y,
+                                                           target_std, epistemic_std_gain, std_scale, epnp_ransac_thres_ratio),
+                cam_mats=cam.data_ptr(), cam_batch=cam.shape[0], u_range=ur.data_ptr(), v_range=vr.data_ptr(), range_batch=ur.shape[0],
+                z_min=float(z_min), istd_thres=float(epnp_istd_thres), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags),
+                valid=valid.data_ptr(), pose=pose.data_ptr(), cov=cov.data_ptr(), tr_radius=tr.data_ptr(), inlier_mask=mask.data_ptr(), diag=_lib.ptr(diag),
+                dims=dims.data_ptr(), dims_var=_lib.ptr(dims_var), **_coord_map_args(_coord_map(coord_2d, dev)), cov_calib_logscale=_lib.ptr(ls),
+                cov_corr_sd=float(cov_correction_sd), cov_calib=_lib.ptr(cov_calib)), torch.cuda.current_stream(dev).cuda_stream))
     out = (valid.view(torch.bool), pose[:, :1], pose[:, 1:], cov, mask.view(torch.bool), dims, dims_var)
     if with_diag:
         out = out + (diag,)
@@ -649,19 +650,18 @@ class PoseFromHeadLaunch:
         # prepared launch holds it for as long as it lives; `inputs['coord_2d']` may be refreshed in place like the other inputs
         cmap = _coord_map(coord_2d, dev)
         self.inputs['coord_2d'] = cmap
-        mp, mh, mw = (cmap.data_ptr(), int(cmap.shape[1]), int(cmap.shape[2])) if cmap is not None else (None, 0, 0)
         self._keep = (ur, vr, mu, sd, nm, ns, cmap)
         self.B = B
-        ratio = pose_head.epnp_ransac_thres_ratio
-        self.args = [i['all_pred'].data_ptr(), ap_dt, i['labels'].data_ptr(), i['flip'].data_ptr(), i['dim'].data_ptr(),
-                     i['dim_var'].data_ptr() if i['dim_var'] is not None else None, i['rois'].data_ptr(),
-                     B, num_classes, int(class_agnostic), h, w, mu.data_ptr(), sd.data_ptr(), nm.data_ptr(), ns.data_ptr(),
-                     float(sdv), float(ref_focal_y), float(epistemic_std_gain), float(pose_head.std_scale), float(ratio) if ratio is not None else -1.0,
-                     i['cam_intrinsic'].data_ptr(), i['cam_intrinsic'].shape[0], ur.data_ptr(), vr.data_ptr(), ur.shape[0],
-                     float(p.z_min), float(p.epnp_istd_thres), int(bool(p.inlier_opt_only)), int(flags),
-                     o['ret_val_u8'].data_ptr(), o['pose'].data_ptr(), o['pose_cov_pred'].data_ptr(), o['tr_radius'].data_ptr(), o['inlier_mask_u8'].data_ptr(),
-                     None, o['dimensions_pred'].data_ptr(), o['dimensions_var'].data_ptr() if o['dimensions_var'] is not None else None, mp, mh, mw,
-                     self.logscale.data_ptr(), float(sdv) if apply_cov_correction else 0.0, o['pose_cov_calib'].data_ptr()]
+        cam = i['cam_intrinsic']
+        self.args = _lib.pack(
+            'mr_pnp_from_head_batched', **_decode_args(i['all_pred'], ap_dt, i['labels'], i['flip'], i['dim'], i['dim_var'], i['rois'], num_classes, class_agnostic,
+                                                       (mu, sd, nm, ns), ref_length, ref_focal_y, target_std, epistemic_std_gain, pose_head.std_scale,
+                                                       pose_head.epnp_ransac_thres_ratio),
+            cam_mats=cam.data_ptr(), cam_batch=cam.shape[0], u_range=ur.data_ptr(), v_range=vr.data_ptr(), range_batch=ur.shape[0],
+            z_min=float(p.z_min), istd_thres=float(p.epnp_istd_thres), inlier_opt_only=int(bool(p.inlier_opt_only)), flags=int(flags),
+            valid=o['ret_val_u8'].data_ptr(), pose=o['pose'].data_ptr(), cov=o['pose_cov_pred'].data_ptr(), tr_radius=o['tr_radius'].data_ptr(),
+            inlier_mask=o['inlier_mask_u8'].data_ptr(), diag=None, dims=o['dimensions_pred'].data_ptr(), dims_var=_lib.ptr(o['dimensions_var']),
+            **_coord_map_args(cmap), cov_calib_logscale=self.logscale.data_ptr(), cov_corr_sd=float(sdv) if apply_cov_correction else 0.0, cov_calib=o['pose_cov_calib'].data_ptr())
         self.graph = None
 
     def run(self, stream=None):

@@ -347,3 +347,67 @@ def test_integration_md_cffi_block_is_the_generated_prototype_text_and_every_sym
     assert set(n for n, _ in protos) == set(hdr) == set(_lib.EXPORTED_SYMBOLS)
     for name, nargs in protos:
         assert hasattr(lib, name) and hdr[name] == nargs, name
+
+
+def test_loaded_signatures_are_the_header_prototypes():
+    """Every `mr_*` prototype of include/monorun_pnp.h: the loaded function has the declared restype and argtypes of the declared
+    length and types, and no argument name repeats within a prototype (``_lib.pack`` goes by name).  The expected ctypes types are
+    derived here from the header text, not by the loader's own mapping."""
+    from monorun_amd import _lib
+    lib = _lib.load()
+    src = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(ROOT, 'include', 'monorun_pnp.h')).read(), flags=re.S)
+    scalar = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64}
+    seen = []
+    for ret, name, args in re.findall(r'^((?:const\s+)?\w+[\s\*]+)(mr_\w+)\s*\(([^)]*)\)\s*;', src, flags=re.M):
+        want_ret = ctypes.c_char_p if ret.split() == ['const', 'char', '*'] else scalar[ret.strip()]
+        args = [] if args.strip() in ('', 'void') else [a.strip() for a in args.split(',')]
+        names = [re.search(r'\w+$', a).group() for a in args]
+        want = [ctypes.c_void_p if '*' in a else scalar[a.replace('const ', '').rsplit(None, 1)[0]] for a in args]
+        f = getattr(lib, name)
+        assert f.restype is want_ret, name
+        assert list(f.argtypes or []) == want, name
+        assert len(set(names)) == len(names), name
+        assert names == (list(_lib.arg_names(name)) + ['stream'] if names and names[-1] == 'stream' else list(_lib.arg_names(name))), name
+        seen.append(name)
+    assert sorted(seen) == sorted(n for n in _lib.EXPORTED_SYMBOLS if n.startswith('mr_')) and len(seen) == 31
+
+
+def test_pack_orders_named_arguments_as_the_abi_does():
+    from monorun_amd import _lib
+    order = ('x2d', 'x2d_strides', 'istd', 'istd_strides', 'x3d', 'x3d_strides', 'in_dtype', 'cam_mats', 'cam_batch', 'ransac_thr', 'B', 'P',
+             'istd_thres', 'flags', 'max_iters', 'init_pose', 'init_mask', 'init_valid', 'diag', 'debug_hypotheses', 'workspace', 'workspace_bytes')
+    assert _lib.arg_names('mr_epnp_ransac_batched') == order                     # include/monorun_pnp.h, without the trailing stream
+    named = {n: k for k, n in enumerate(order)}
+    assert _lib.pack('mr_epnp_ransac_batched', **dict(reversed(list(named.items())))) == list(range(len(order)))
+    with pytest.raises(TypeError, match='max_iters'):
+        _lib.pack('mr_epnp_ransac_batched', **{n: v for n, v in named.items() if n != 'max_iters'})
+    with pytest.raises(TypeError, match='u_range'):
+        _lib.pack('mr_epnp_ransac_batched', u_range=0, **named)
+    assert _lib.table_args('mr_epnp_ransac_grouped') == ('x2d', 'istd', 'x3d', 'cam_mats', 'ransac_thr', 'init_pose', 'init_mask', 'init_valid', 'diag')
+    assert _lib.table_args('mr_epnp_ransac_batched') == ()
+
+
+def test_launch_set_members_must_agree_by_argument_name():
+    """What PnPEpnpGroupLaunch refuses, on the members' named arguments alone (the launch classes need a HIP device): one mismatch per
+    argument the set passes once, and per pointer that must be given or left out by all members."""
+    import importlib
+    pu = importlib.import_module('monorun_amd.ops.least_squares.pnp_uncert')      # (the package re-exports the function under this name)
+    st = lambda *v: (ctypes.c_int64 * 3)(*v)
+    init = dict(x2d=1, x2d_strides=st(1568, 1, 784), istd=2, istd_strides=st(1568, 1, 784), x3d=3, x3d_strides=st(2352, 1, 784), in_dtype=0, cam_mats=4,
+                cam_batch=1, ransac_thr=5, B=64, P=784, istd_thres=0.6, flags=0, max_iters=30, init_pose=6, init_mask=7, init_valid=8, diag=None,
+                debug_hypotheses=None, workspace=9, workspace_bytes=10)
+    lm = dict(range_batch=1, z_min=0.5, inlier_opt_only=1, flags=0, diag=None, valid=11, pose=12)
+    other = dict(init, x2d=21, x2d_strides=st(1568, 1, 784), ransac_thr=25, init_pose=26, workspace=29)     # own tensors, equal strides: agrees
+    pu._require_agreement([init, other, init], pu._SET_INIT, 'X')
+    pu._require_agreement([lm, dict(lm, valid=31, pose=32)], pu._SET_LM, 'X')
+    msg = 'the members of a group must share shape, strides, dtype, camera batching, thresholds and flags'
+    for change in (dict(x2d_strides=st(1568, 784, 1)), dict(istd_strides=st(2, 1, 784)), dict(x3d_strides=st(2352, 784, 1)), dict(in_dtype=1),
+                   dict(cam_batch=64), dict(B=32), dict(P=144), dict(istd_thres=0.7), dict(flags=4), dict(max_iters=20), dict(ransac_thr=None), dict(diag=40)):
+        with pytest.raises(ValueError) as e:
+            pu._require_agreement([init, dict(init, **change)], pu._SET_INIT, 'shape, strides, dtype, camera batching, thresholds and flags')
+        assert str(e.value) == msg, change
+    msg = 'the members of a group must share range batching, z_min, inlier_opt_only and flags'
+    for change in (dict(range_batch=64), dict(z_min=0.4), dict(inlier_opt_only=0), dict(flags=0x20), dict(diag=41)):
+        with pytest.raises(ValueError) as e:
+            pu._require_agreement([lm, lm, dict(lm, **change)], pu._SET_LM, 'range batching, z_min, inlier_opt_only and flags')
+        assert str(e.value) == msg, change

@@ -401,11 +401,12 @@ def test_grouped_calls_equal_the_calls_one_by_one(dev):
     with pytest.raises(ValueError):
         PnPEpnpGroupLaunch([refs[0], refs[1], refs[2], refs[3], refs[6]] * 2)
     g = PnPEpnpGroupLaunch([refs[2], refs[3]])
-    bad = list(g.args); bad[0] = 9
+    at = _lib.arg_names('mr_epnp_ransac_grouped').index
+    bad = list(g.args); bad[at('ncalls')] = 9
     assert lib.mr_epnp_ransac_grouped(*bad, None) == -1
-    bad = list(g.args); thr = (ctypes.c_void_p * 2)(g.args[10][0], None); bad[10] = thr
+    bad = list(g.args); thr = (ctypes.c_void_p * 2)(g.args[at('ransac_thr')][0], None); bad[at('ransac_thr')] = thr
     assert lib.mr_epnp_ransac_grouped(*bad, None) == -1
-    bad = list(g.args); bad[21] = 1024
+    bad = list(g.args); bad[at('workspace_bytes')] = 1024
     assert lib.mr_epnp_ransac_grouped(*bad, None) == -1                   # workspace too small for the whole group
     torch.cuda.synchronize()
 

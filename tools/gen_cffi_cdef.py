@@ -8,22 +8,11 @@ than plain integer #defines, no comments, no extern "C").  INTEGRATION.md §3 ca
 """
 import os
 import re
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def header_prototypes(path=os.path.join(ROOT, 'include', 'monorun_pnp.h')):
-    """[(name, 'return type', ['arg type name', ...])] for every function the header declares."""
-    src = open(path).read()
-    src = re.sub(r'/\*.*?\*/', ' ', src, flags=re.S)
-    src = re.sub(r'//[^\n]*', ' ', src)
-    src = '\n'.join(l for l in src.split('\n') if not l.lstrip().startswith('#') and 'extern "C"' not in l and l.strip() != '}')
-    out = []
-    for m in re.finditer(r'([A-Za-z_][\w\s\*]*?)\b(\w+)\s*\(([^()]*)\)\s*;', src):
-        ret, name, args = ' '.join(m.group(1).split()), m.group(2), m.group(3)
-        args = [' '.join(a.split()).replace(' *', ' *').replace('* ', '*') for a in args.split(',')] if args.strip() not in ('', 'void') else []
-        out.append((name, ret, args))
-    return out
+sys.path.insert(0, ROOT)
+from monorun_amd._lib import header_prototypes  # noqa: E402  (the loader's own parser of the header: one reader of the prototypes)
 
 
 def header_int_defines(path=os.path.join(ROOT, 'include', 'monorun_pnp.h')):
@@ -53,7 +42,6 @@ def update_integration_md(path=os.path.join(ROOT, 'INTEGRATION.md')):
 
 
 if __name__ == '__main__':
-    import sys
     if '--update' in sys.argv:
         update_integration_md()
     else:

@@ -44,7 +44,7 @@ for B in (100, 1024):
     fwd.run()
     torch.cuda.synchronize()
     x2d, istd, x3d = x[:3]
-    cam, ur, vr = fwd.keep[3], fwd.keep[4], fwd.keep[5]
+    cam, ur, vr = fwd.keep['cam_mats'], fwd.keep['u_range'], fwd.keep['v_range']
     g = torch.Generator().manual_seed(0)
     gp = torch.randn(B, 4, generator=g).to(dev)
     gc = torch.randn(B, 16, generator=g).to(dev)
