@@ -23,7 +23,10 @@
     uint16_t *slist = (uint16_t *)(tile_base + (size_t)5 * np * sizeof(T));
     uint16_t *slist2 = slist + np;
     unsigned *smask = (unsigned *)(slist2 + np);                            // [(P + 31) / 32]: the inlier mask, one bit per point
+    // [kEpKeptBallots][nca]: the counting loop's ballots, per hypothesis of the round and 64-candidate chunk (rounds of at most kEpKeptBallots hypotheses)
+    unsigned long long *sbal_h = (unsigned long long *)(tile_base + ((epnp_consensus_tile_bytes(a) + 7) & ~(size_t)7));
 
+    EPC_STAMP(8); EPC_STAMP(0);
     const EpCallView cv = ep_call_view(ea, b);
     ep_load_geometry<T>(cv, b, P, NT, tl);
     for (int i = tid; i < n; i += NT) slist[i] = ea.w.cand[(long long)b * ea.w.pstride + i];
@@ -56,10 +59,14 @@
         for (int i = tid; i < 4 * 32; i += NT) scnt[i] = 0;
         for (int i = tid; i < (P + 31) >> 5; i += NT) smask[i] = 0u;
         __syncthreads();
+        EPC_STAMP(1);
 
         // ---- consensus of every hypothesis over the candidates
         const float thr2 = (float)((double)thr_given * (double)thr_given);
         const int nct = (n + NT - 1) / NT;
+        const int nlc = (n + 63) >> 6;
+        // a round of few hypotheses keeps every ballot: chunk (i0 + k) * WPO + wid holds the candidates 64 chunk ... + 63, the numbering of the list compaction below
+        const bool keep_ballots = ea.h1 - ea.h0 <= kEpKeptBallots;
         for (int i0 = 0; i0 < nct; i0 += 4) {
             float po[4][3], pi[4][2];
             bool lv[4];
@@ -77,12 +84,16 @@
                 for (int i = 0; i < 3; ++i) t[i] = shyp[h * 12 + 9 + i];
                 int c = 0;
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    c += __popcll(__ballot(lv[k] && ep_is_inlier(cam, R, t, po[k][0], po[k][1], po[k][2], pi[k][0], pi[k][1], thr2)));
+                for (int k = 0; k < 4; ++k) {
+                    const unsigned long long bal = __ballot(lv[k] && ep_is_inlier(cam, R, t, po[k][0], po[k][1], po[k][2], pi[k][0], pi[k][1], thr2));
+                    c += __popcll(bal);
+                    if (keep_ballots && lane == 0 && (i0 + k) * WPO + wid < nlc) sbal_h[(h - ea.h0) * a.nca + (i0 + k) * WPO + wid] = bal;
+                }
                 if (lane == 0) scnt[wid * 32 + h] += c;
             }
         }
         __syncthreads();
+        EPC_STAMP(2);
 
         // ---- RANSAC's loop replayed over the counts, in RNG order (ptsetreg.cpp run), as far as this round's hypotheses reach
         // (by wave 0 alone, its state through LDS: RANSACUpdateNumIters is a pow and two logs of the device math library — ~600
@@ -101,6 +112,7 @@
         __syncthreads();
         it = scnt[128]; niters = scnt[129]; best = scnt[130]; besth = scnt[131];
         iters_run = it;
+        EPC_STAMP(3);
         if (it < niters && ea.h1 < kEpMaxIters) {                  // the loop goes on: the remaining hypotheses are solved in the next round
             if (tid == 0) { meta[EP_M_PENDING] = 1; meta[EP_M_NITERS] = niters; meta[EP_M_BEST] = best; meta[EP_M_BESTH] = besth; meta[EP_M_ITERS] = it; }
             // ... on the samples of the hypotheses [h1, niters), which the front launch left to this one: their correspondences from the
@@ -113,43 +125,52 @@
                 float *s = ea.w.samp + ((long long)b * kEpMaxIters + h) * kEpSampRec + 5 * i;
                 s[0] = o[0]; s[1] = o[1]; s[2] = o[2]; s[3] = im[0]; s[4] = im[1];
             }
+            EPC_STAMP(7); EPC_STAMP(9);
             return;
         }
         if (best <= 0) ok = false;
         else {
             // ---- inliers of the best model: mask in point space, compacted list (ascending)
-            double R[9], t[3];
+            // the best model was counted in THIS round and its ballots were kept: they are these bits (the same predicate on the same operands).  Otherwise
+            // (the first round's best model in the second round, a round wider than kEpKeptBallots) the test is evaluated again
+            const bool kept = keep_ballots && besth >= ea.h0 && besth < hend;
+            const unsigned long long *bl = kept ? sbal_h + (besth - ea.h0) * a.nca : sball;
+            if (!kept) {
+                double R[9], t[3];
 #pragma unroll
-            for (int i = 0; i < 9; ++i) R[i] = shyp[besth * 12 + i];
+                for (int i = 0; i < 9; ++i) R[i] = shyp[besth * 12 + i];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) t[i] = shyp[besth * 12 + 9 + i];
-            const int nlc = (n + 63) >> 6;
-            for (int i = 0; i < nct; ++i) {
-                const int qi = i * NT + tid;
-                const bool lvq = qi < n;
-                const int pidx = slist[lvq ? qi : 0];
-                float o[3], im[2];
-                fetch(pidx, o, im);
-                const bool in = lvq && ep_is_inlier(cam, R, t, o[0], o[1], o[2], im[0], im[1], thr2);
-                if (in) atomicOr(&smask[pidx >> 5], 1u << (pidx & 31));
-                const unsigned long long bal = __ballot(in);
-                if (lane == 0 && i * WPO + wid < nlc) sball[i * WPO + wid] = bal;
+                for (int i = 0; i < 3; ++i) t[i] = shyp[besth * 12 + 9 + i];
+                for (int i = 0; i < nct; ++i) {
+                    const int qi = i * NT + tid;
+                    const bool lvq = qi < n;
+                    const int pidx = slist[lvq ? qi : 0];
+                    float o[3], im[2];
+                    fetch(pidx, o, im);
+                    const bool in = lvq && ep_is_inlier(cam, R, t, o[0], o[1], o[2], im[0], im[1], thr2);
+                    const unsigned long long bal = __ballot(in);
+                    if (lane == 0 && i * WPO + wid < nlc) sball[i * WPO + wid] = bal;
+                }
+                __syncthreads();
             }
-            __syncthreads();
             int ex0, ex1;
-            n_fit = scan_chunks(sball, nlc, lane, ex0, ex1);
+            n_fit = scan_chunks(bl, nlc, lane, ex0, ex1);
             for (int i = 0; i < nct; ++i) {
                 const int chunk = i * WPO + wid;
                 if (chunk >= nlc) break;
-                const unsigned long long bal = sball[chunk];
+                const unsigned long long bal = bl[chunk];
                 const int base = chunk_base(chunk, ex0, ex1);
-                if ((bal >> lane) & 1ull) slist2[base + __popcll(bal & ((1ull << lane) - 1ull))] = slist[chunk * 64 + lane];
+                if ((bal >> lane) & 1ull) {
+                    const int pidx = slist[chunk * 64 + lane];
+                    slist2[base + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)pidx;
+                    atomicOr(&smask[pidx >> 5], 1u << (pidx & 31));
+                }
             }
             list = slist2;
             __syncthreads();
-            for (int p = tid; p < P; p += NT) cv.init_mask[(long long)b * P + p] = (uint8_t)((smask[p >> 5] >> (p & 31)) & 1u);
         }
     } else __syncthreads();
+    EPC_STAMP(4);
 
     if (ok) {
         // ---- EPnP on the whole set (the re-fit on the inliers, or plain solvePnP): A) centroid, covariance -> control points,
@@ -193,8 +214,16 @@
 #pragma unroll
                 for (int i = 0; i < 9; ++i) { sprep[12 + i] = ci[i]; ea.w.prep_r[(long long)b * 24 + (12 + i)] = ci[i]; }
             }
+        } else {
+            // ... while the other waves, which have nothing to do until the control points exist, store what depends on none of it: the inlier mask
+            // in point space and the re-fit's list
+            const int t = tid - 64;
+            if (mode == EP_MODE_RANSAC)
+                for (int p = t; p < P; p += NT - 64) cv.init_mask[(long long)b * P + p] = (uint8_t)((smask[p >> 5] >> (p & 31)) & 1u);
+            for (int i = t; i < nn; i += NT - 64) ea.w.fit[(long long)b * ea.w.pstride + i] = list[i];
         }
         __syncthreads();
+        EPC_STAMP(5);
 
         // what every point needs of the above is wave-uniform: into scalar registers (the accumulators below want the vector ones)
         double cws[4][3], ci[9];
@@ -213,6 +242,7 @@
         static_assert(WPO == 4, "one M^T M part per wave");
         if (wid == 0) EP_MTM_DO(0); else if (wid == 1) EP_MTM_DO(1); else if (wid == 2) EP_MTM_DO(2); else EP_MTM_DO(3);
 #undef EP_MTM_DO
-        for (int i = tid; i < nn; i += NT) ea.w.fit[(long long)b * ea.w.pstride + i] = list[i];
+        EPC_STAMP(6);
     }
     if (tid == 0) { meta[EP_M_NFIT] = n_fit; meta[EP_M_REFIT] = ok ? (use_ransac_refit_f64 ? 3 : 1) : 0; meta[EP_M_ITERS] = iters_run; meta[EP_M_BEST] = best; meta[EP_M_BESTH] = besth; }
+    EPC_STAMP(7); EPC_STAMP(9);

@@ -74,6 +74,9 @@ struct EpnpStageArgs {
     double *dbg_hyp;        // out (B,30,12) or null: every hypothesis' R (after the Rodrigues round trip) and t — tests
     int max_iters;
     int h0, h1;             // the hypotheses [h0, h1) of this round (round 0: h0 = 0; round 1: the rest, for the objects still pending)
+#ifdef MR_DEBUG_STAMPS
+    unsigned long long *cstamps;      // development builds: (B,24) cycle stamps of the consensus body (EPC_STAMP), or null
+#endif
 };
 
 size_t epnp_work_bytes(int B, int P, EpnpWork *w, unsigned char *base) {
@@ -639,13 +642,18 @@ constexpr int kEpPoseThreads = 192;     // the re-fit's workgroup: one wave per 
 #ifdef MR_DEBUG_STAMPS
 #define EP_STAMP(i) do { if (ea.h0 == 0 && ea.p.stamps && threadIdx.x == 0 && blockIdx.x < 64) ea.p.stamps[(long long)blockIdx.x * 24 + (i)] = __builtin_readcyclecounter(); } while (0)
 #define EP_EIG_STAMPS (ea.h0 == 0 ? ea.p.stamps : nullptr)
+// the consensus body's phases (epnp_consensus_body.inc), thread 0 of EVERY object, into a buffer of its own (the LM launch stamps every object too): 24 per object,
+// 12 per round — 0 start | 1 tile loaded | 2 counts done | 3 loop replayed | 4 mask + list done | 5 control points done | 6 moments done | 7 end; 8, 9 = the 100 MHz
+// clock at start and end (tools/gpu_consensus_stamps.py)
+#define EPC_STAMP(i) do { if (ea.cstamps && threadIdx.x == 0) ea.cstamps[((long long)b * 2 + (ea.h0 > 0 ? 1 : 0)) * 12 + (i)] = (i) >= 8 ? wall_clock64() : __builtin_readcyclecounter(); } while (0)
 #else
 #define EP_STAMP(i) do { } while (0)
 #define EP_EIG_STAMPS nullptr
+#define EPC_STAMP(i) do { } while (0)
 #endif
 #ifndef MR_EP_CONS_WAVES
 #define MR_EP_CONS_WAVES 5       // waves per SIMD the consensus launch is compiled for: 5 = 96 registers with 7 spilled (32 B of scratch per lane, all of it in wave 0's control-point
-                                 // block: ep_eig3), five objects per CU by registers and 5 x 21.9 KB of LDS, which leaves 50 KB of the CU to the other streams' workgroups; 4 = 105
+                                 // block: ep_eig3), five objects per CU by registers and 5 x 23.2 KB of LDS (21.9 when this was measured), which leaves 44 KB of the CU to the other streams' workgroups; 4 = 105
                                  // registers, no scratch.  Sets of five on four streams, eight fresh processes each, alternating: 12.30 | 11.91 M solves/s (main: 11.75); in flight
                                  // the LM launch is resident 460 | 514 us (539) — profiles/r07_bench_ab.txt, r07_inflight_trace.txt.  Round 6 (31.8 KB tile): same speed either way
 #endif
@@ -862,15 +870,18 @@ __global__ void __launch_bounds__(64, MR_EP_QUAD_WAVES) epnp_hyp_kernel(const Ep
 }
 
 // ------------------------------------------------------------------------------------------------ consensus + the re-fit's sums
-size_t epnp_consensus_lds_bytes(const PnpArgs &a) {      // 21.9 KB at P = 784, fp32 (round 6: 31.8)
+constexpr int kEpKeptBallots = 10;      // rounds of at most this many hypotheses keep the counting loop's ballots (launch sets: 3, one call at a time: 10)
+__host__ __device__ inline size_t epnp_consensus_tile_bytes(const PnpArgs &a) {      // from the tile's base: GeoTile, the two lists, the inlier mask
     const size_t np = (size_t)((a.P + 7) & ~7);
+    return 5 * np * a.elem_size + 2 * sizeof(uint16_t) * np + sizeof(unsigned) * ((a.P + 31) >> 5);
+}
+size_t epnp_consensus_lds_bytes(const PnpArgs &a) {      // 23.2 KB at P = 784, fp32 (rounds 7 to 9: 21.9, round 6: 31.8)
     size_t n = 0;
     n += sizeof(double) * (30 * 12);
     n += sizeof(unsigned long long) * a.nca;
     n += sizeof(int) * (4 * 32 + 4);
-    n += 5 * np * a.elem_size;                            // GeoTile
-    n += 2 * sizeof(uint16_t) * np;
-    n += sizeof(unsigned) * ((a.P + 31) >> 5);             // inlier mask, one bit per point
+    n += (epnp_consensus_tile_bytes(a) + 7) & ~(size_t)7; // GeoTile, 2 lists of uint16, inlier mask (one bit per point); the ballots below on an 8-byte boundary
+    n += sizeof(unsigned long long) * kEpKeptBallots * a.nca;      // the kept ballots: 1.25 KB at P = 784
     return (n + 15) & ~(size_t)15;
 }
 

@@ -809,6 +809,9 @@ bool build_plan(PairwisePlan &pl, int P) {
 
 std::atomic<int> g_last_hip_error{0};
 unsigned long long *g_stamps = nullptr;
+#ifdef MR_DEBUG_STAMPS
+unsigned long long *g_cons_stamps = nullptr;
+#endif
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { g_last_hip_error = (int)e_; return MR_ERR_HIP; } } while (0)
 
 // What the heuristics below need to know about the device, read once per device from hipGetDeviceProperties (an MI355X reports
@@ -1157,6 +1160,10 @@ int mr_pnp_last_hip_error(void) { return g_last_hip_error; }
 
 // development aid (not in the public header): device buffer of (B,10) u64 cycle stamps, or NULL to disable
 void mr_pnp_debug_set_stamps(unsigned long long *dev_ptr) { g_stamps = dev_ptr; }
+#ifdef MR_DEBUG_STAMPS
+// -DMR_DEBUG_STAMPS builds only: device buffer of (B,24) u64 stamps of the consensus launches (EPC_STAMP, tools/gpu_consensus_stamps.py), or NULL
+void mr_pnp_debug_set_consensus_stamps(unsigned long long *dev_ptr) { g_cons_stamps = dev_ptr; }
+#endif
 
 // Occupies one wavefront of the device for `microseconds` (100 MHz constant clock).  PnPPipeline uses it to find out which of
 // its streams the runtime really runs side by side: HIP maps streams onto a small number of hardware queues (4 per priority level
@@ -1370,6 +1377,9 @@ static int epnp_ransac_launch(
     int rc;
     if ((rc = choose_mean_order(a)) != MR_OK) return rc;
     a.stamps = g_stamps;
+#ifdef MR_DEBUG_STAMPS
+    sa.cstamps = g_cons_stamps;
+#endif
     sa.init_pose = init_pose[0]; sa.init_mask = init_mask[0]; sa.init_ok = init_valid[0]; sa.diag = diag ? diag[0] : nullptr; sa.dbg_hyp = debug_hypotheses; sa.max_iters = max_iters;
     sa.ncalls = ncalls; sa.group_B = B;
     hipStream_t st = (hipStream_t)stream;
