@@ -1,4 +1,5 @@
-"""ctypes loader / builder for libmonorun_pnp.so (the C ABI declared in include/monorun_pnp.h).
+"""ctypes loader / builder for libmonorun_pnp.so (the C ABI declared in include/monorun_pnp.h and, for the head kernels behind the
+PnP, include/monorun_heads.h).
 
 The library is built in-tree by hipcc for gfx950 (``build()``; also driven by
 ``__graft_entry__.build()``) and loaded with ctypes — cffi, which the reference uses
@@ -16,6 +17,7 @@ _ROOT = os.path.dirname(_HERE)
 SRC = os.path.join(_HERE, 'csrc', 'monorun_pnp.hip')
 INCLUDE = os.path.join(_ROOT, 'include')
 HEADER = os.path.join(INCLUDE, 'monorun_pnp.h')
+HEADS_HEADER = os.path.join(INCLUDE, 'monorun_heads.h')      # the head kernels' entry points: same library, a header of their own
 SO = os.environ.get('MR_PNP_SO') or os.path.join(_HERE, 'libmonorun_pnp.so')     # MR_PNP_SO: A/B-test another build of the library
 
 MR_F32, MR_F16, MR_F64, MR_BF16 = 0, 1, 2, 3
@@ -28,6 +30,7 @@ MR_WAVES_SHIFT = 8
 MR_LM_MAXIT_SHIFT = 16
 MR_EPNP_FIRST_ROUND_SHIFT = 24
 MR_IOU3D_GEOMETRIC_HEIGHT = 0x1
+MR_SCORE_SIGMOID = 0x1
 
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared']
 
@@ -39,7 +42,7 @@ def _stale():
         return True
     t = os.path.getmtime(SO)
     csrc = os.path.join(_HERE, 'csrc')
-    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER]
+    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER, HEADS_HEADER]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -79,19 +82,21 @@ def _ctype(name, ctype):
     if '*' in ctype:
         return ctypes.c_void_p
     if ctype not in _CTYPES:
-        raise TypeError(f'{name}: include/monorun_pnp.h uses the type {ctype!r}, which the loader has no ctypes mapping for')
+        raise TypeError(f'{name}: its header uses the type {ctype!r}, which the loader has no ctypes mapping for')
     return _CTYPES[ctype]
 
 
 def _prototype(fn):
     """(restype, [argtypes], (argument names without the trailing stream), (names of the per-call pointer tables `T *const *`),
-    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h declares it.  The header is read once."""
+    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h or include/monorun_heads.h declares it.  The headers
+    are read once."""
     global _prototypes
     if _prototypes is None:
         protos = {}
-        for name, ret, args in header_prototypes():
+        for name, ret, args in header_prototypes() + header_prototypes(HEADS_HEADER):
             if not name.startswith('mr_'):
                 continue                                # the reference's cffi symbols of ext.h: declared by hand in load()
+            assert name not in protos, f'{name}: declared twice'
             decl = [re.fullmatch(r'(.*?)(\w+)', a).groups() for a in args]
             names = tuple(n for _, n in decl)
             assert len(set(names)) == len(names), f'{name}: argument names repeat'
@@ -132,7 +137,7 @@ def ptr(t):
 
 def load():
     """Return the ctypes handle; raises if the library has not been built.  restype / argtypes of every `mr_*` entry point come
-    from its prototype in include/monorun_pnp.h (``_prototype``)."""
+    from its prototype in include/monorun_pnp.h or include/monorun_heads.h (``_prototype``)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -142,7 +147,7 @@ def load():
             '(hipcc --offload-arch=gfx950). monorun_amd has no CPU fallback.')
     lib = ctypes.CDLL(SO)
     vp, i32 = ctypes.c_void_p, ctypes.c_int
-    for name, _, _ in header_prototypes():
+    for name, _, _ in header_prototypes() + header_prototypes(HEADS_HEADER):
         if name.startswith('mr_'):
             f = getattr(lib, name)
             f.restype, argtypes = _prototype(name)[:2]
@@ -175,3 +180,5 @@ def check(code):
 EXPORTED_SYMBOLS = ('mr_pnp_version', 'mr_spin', 'mr_pick_waves', 'mr_pnp_error_string', 'mr_pnp_last_hip_error', 'mr_pnp_device_count',
                     'mr_pnp_uncert_batched', 'mr_epnp_ransac_batched', 'mr_epnp_ransac_grouped', 'mr_epnp_workspace_bytes', 'mr_pnp_uncert_from_init_batched', 'mr_pnp_uncert_from_init_grouped', 'mr_pnp_uncert_from_epnp_grouped', 'mr_cov_symeig_rule', 'mr_pnp6_refine_batched', 'mr_pnp_exact_hessian_batched', 'mr_pnp_uncert_backward_batched', 'pnp_uncert', 'mr_noc_decode_batched', 'mr_pnp_from_head_batched', 'mr_nms_bev_batched', 'mr_bbox3d_overlaps_aligned', 'mr_uncert_projection', 'mr_uncert_projection_backward', 'mr_robust_kl_workspace_bytes', 'mr_robust_kl_loss', 'mr_robust_kl_loss_backward', 'pnp_noc_uncert', 'pnp_noc_cov_uncert', 'mr_pnp_noc_batched',
                     'mr_kitti_overlaps', 'mr_kitti_match_workspace_bytes', 'mr_kitti_match', 'mr_roi_align_avg')
+# the entry points of include/monorun_heads.h: the same library, outside the cffi surface of monorun_pnp.h
+HEADS_EXPORTED_SYMBOLS = ('mr_score_head_forward',)

@@ -12,6 +12,8 @@ reduced as mmdet's ``weighted_loss`` reduces ('none' | 'mean' | 'sum', optional 
 ``RobustKLLoss`` is the NOC head's projection loss (``loss_proj`` of ``UncertProjectionHead``), the only loss that
 trains the NOC head in the shipped configs with ``loss_noc=None``.  Its reduced forms on CUDA run HIP kernels; the rest runs in torch.
 
+``CrossEntropyLoss`` is the sigmoid form of mmdet's loss of that name, the score head's ``loss_score``, in torch.
+
 ``build_loss`` builds a loss config dict: with mmdet's registry when mmdet imports and knows the type, else with this module's
 registry.  A type neither knows becomes an ``UnbuiltLoss``, which raises, naming the type, only when it is called.
 """
@@ -185,7 +187,31 @@ class RobustKLLoss(nn.Module):
         return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
 
 
-LOSSES = {'KLLossMV': KLLossMV, 'RobustKLLoss': RobustKLLoss}
+class CrossEntropyLoss(nn.Module):
+    """The sigmoid form of mmdet's ``CrossEntropyLoss`` (``use_sigmoid=True``), the score head's default ``loss_score``:
+    ``binary_cross_entropy_with_logits(pred, target)`` per element, then :func:`weight_reduce_loss`.  ``weight`` is per sample:
+    it is reshaped to ``pred``'s shape, so an (N,) weight scales the rows of an (N, 1) loss and never broadcasts to (N, N).
+    The softmax and mask forms are not restated: ``use_sigmoid=False`` raises."""
+
+    def __init__(self, use_sigmoid=True, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        if not use_sigmoid:
+            raise NotImplementedError('monorun_amd.losses.CrossEntropyLoss restates the sigmoid form only (use_sigmoid=True)')
+        self.use_sigmoid = True
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+
+    def forward(self, cls_score, label, weight=None, avg_factor=None, reduction_override=None):
+        if reduction_override not in (None, 'none', 'mean', 'sum'):
+            raise ValueError(f'CrossEntropyLoss: reduction_override {reduction_override!r}')
+        reduction = reduction_override if reduction_override else self.reduction
+        loss = nn.functional.binary_cross_entropy_with_logits(cls_score, label.to(cls_score.dtype).reshape(cls_score.shape), reduction='none')
+        if weight is not None:
+            weight = weight.to(loss.dtype).reshape(loss.shape)
+        return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+LOSSES = {'KLLossMV': KLLossMV, 'RobustKLLoss': RobustKLLoss, 'CrossEntropyLoss': CrossEntropyLoss}
 
 
 class UnbuiltLoss:
