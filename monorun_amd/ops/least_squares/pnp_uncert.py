@@ -548,11 +548,13 @@ def exact_hessian_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range
 
 
 def pnp_uncert_backward_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, pose4, inlier_mask_u8, valid_u8, grad_pose,
-                               cov=None, grad_cov=None, z_min=0.5, lm_all_points=False, needs=(True, True, True), with_status=False):
+                               cov=None, grad_cov=None, z_min=0.5, lm_all_points=False, needs=(True, True, True), with_status=False, out=None):
     """Backward of the 4-DoF op (``mr_pnp_uncert_backward_batched``): gradients of a loss L(pose, cov) with respect to
     the correspondences at the pose4 (B,4) f32 / inlier_mask_u8 (B,P) u8 | None / valid_u8 (B,) u8 the forward returned.
     grad_pose (B,4) = dL/d[yaw, t] or None (zero); cov (B,4,4) = the returned covariance and grad_cov (B,4,4) = dL/dcov, both or None.
     lm_all_points: the LM refined every point (inlier_opt_only=False).  needs: which of (x2d, istd, x3d) to compute.
+    out: the caller's (grad_x2d, grad_istd, grad_x3d) buffers to write instead of new ones (f32, contiguous, on the inputs' device; None where
+    `needs` is False); every row of every buffer is written.
     Returns (grad_x2d f32 (B,P,2) | None, grad_istd f32 (B,P,2) | None, grad_x3d f32 (B,P,3) | None, status u8 (B,) | None)."""
     lib = _lib.load()
     dev, B, P, common, _ = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range,
@@ -564,9 +566,11 @@ def pnp_uncert_backward_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u
     pose, gp, c, gc = conv(pose4, B, 4), conv(grad_pose, B, 4), conv(cov, B, 16), conv(grad_cov, B, 16)
     mask = inlier_mask_u8.detach().to(device=dev, dtype=torch.uint8).contiguous() if inlier_mask_u8 is not None else None
     valid = valid_u8.detach().to(device=dev, dtype=torch.uint8).contiguous()
-    g2 = torch.empty(B, P, 2, **f32) if needs[0] else None
-    gw = torch.empty(B, P, 2, **f32) if needs[1] else None
-    g3 = torch.empty(B, P, 3, **f32) if needs[2] else None
+    if out is None:
+        out = [torch.empty(B, P, ch, **f32) if n else None for n, ch in zip(needs, (2, 2, 3))]
+    for t, n, ch in zip(out, needs, (2, 2, 3)):
+        assert (t is None) == (not n) and (t is None or (t.shape == (B, P, ch) and t.dtype == torch.float32 and t.device == dev and t.is_contiguous()))
+    g2, gw, g3 = out
     status = torch.empty(B, device=dev, dtype=torch.uint8) if with_status else None
     if B > 0:
         with torch.cuda.device(dev):

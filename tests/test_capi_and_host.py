@@ -231,8 +231,9 @@ def test_capi_argument_validation_without_a_gpu():
     def bw(B=4, P=784, x2d=p, pose=p, valid=p, cov=None, gcov=None, cam_batch=1, range_batch=1, dtype=F32):
         return lib.mr_pnp_uncert_backward_batched(x2d, st, p, st, p, st, dtype, p, cam_batch, p, p, range_batch, pose, p, valid, 1, p, cov, gcov,
                                                   B, P, 0.5, p, p, p, p, None)
-    assert bw(B=0) == 0 and bw(B=0, cov=p) == 0
-    assert bw(B=-1) == -1 and bw(P=0) == -1 and bw(B=0, P=0) == -1
+    assert bw(B=0) == 0 and bw(B=0, cov=p) == 0 and bw(B=0, x2d=None, pose=None, valid=None) == 0          # an empty batch touches no pointer
+    assert bw(B=-1) == -1 and bw(P=0) == -1 and bw(P=-1) == -1 and bw(B=0, P=0) == -1
+    assert bw(cam_batch=3) == -1 and bw(cam_batch=0) == -1 and bw(cam_batch=5) == -1 and bw(range_batch=0) == -1
     assert bw(x2d=None) == -1 and bw(pose=None) == -1 and bw(valid=None) == -1 and bw(pose=None, cov=p, gcov=p) == -1
     assert bw(cov=p) == -1 and bw(gcov=p) == -1 and bw(cov=p, gcov=p, cam_batch=3) == -1 and bw(range_batch=2) == -1
     assert bw(dtype=7) == -2 and bw(dtype=7, cov=p, gcov=p) == -2
