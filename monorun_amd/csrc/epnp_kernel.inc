@@ -383,14 +383,14 @@ __device__ __forceinline__ void ep_rodrigues_to_mat(const double (&r)[3], double
 }
 
 // ---------------------------------------------------------------------------- sample-level pieces
-struct EpCam { double fx, fy, cx, cy; };
+using EpCam = K4;       // { fx, fy, cx, cy } in doubles (pnp_kernel.inc)
 
 __device__ __forceinline__ double ep_psum5(double t0, double t1, double t2, double t3, double t4) {
     MR_EXACT
     return ((t0 + t1) + (t2 + t3)) + t4;             // the 64-partial butterfly (strides 32, 16, 1, 2, 4, 8) on five occupied partials
 }
 
-// (a copy of stage 1 of pnp_uncert_kernel — that kernel's text is frozen so that its tuned ISA does not move, tools/isa_diff.sh)
+// (own text, like stage 1 of pnp_uncert_kernel: with the sums and the list loop as shared functions the code of epnp_front_kernel moves — HISTORY.md, round 12)
 // stage 1 of the per-object kernels: istd inlier mask with numpy's float32 summation order (pnp_uncert_cpu.py:164-168) and the
 // ascending candidate list.  Three barriers in all: after the sums, after the ballots, after the list (the last one is the
 // caller's).  Returns the number of candidates = entries of slist.  pl_*: the summation-plan entries this lane prefetched.

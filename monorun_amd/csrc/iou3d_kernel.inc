@@ -20,12 +20,7 @@
 //   MR_IOU3D_GEOMETRIC_HEIGHT: max_z = max(box_top, qbox_top) — the geometric overlap, as the numpy sibling (:84) and the N x K form (:28).
 // Composition in fp32, operation for operation (no contraction):
 //   iw = clamp(min_z - max_z, 0); v1 = (l*h)*w; v2 likewise; inc = iw * rinc; ua = v1 + v2 - inc | v1 | v2 | 1 (criterion -1 | 0 | 1 | 2);
-//   iou = clamp(inc / clamp(ua, 1e-6), 0, 1).  min / max / clamp propagate NaN, as torch's do.
-
-__device__ __forceinline__ float iou3d_min(float a, float b) { return (a != a || a < b) ? a : b; }     // torch.min / np.minimum
-__device__ __forceinline__ float iou3d_max(float a, float b) { return (a != a || a > b) ? a : b; }     // np.maximum
-__device__ __forceinline__ float iou3d_clamp_lo(float x, float lo) { return x < lo ? lo : x; }         // clamp(min=lo), NaN stays
-__device__ __forceinline__ float iou3d_clamp_hi(float x, float hi) { return x > hi ? hi : x; }
+//   iou = clamp(inc / clamp(ua, 1e-6), 0, 1).  min / max / clamp propagate NaN, as torch's do (nan_min ... clamp_hi, kitti_eval_kernel.inc).
 
 __global__ void __launch_bounds__(256) bbox3d_overlaps_aligned_kernel(const float *__restrict__ boxes, long long boxes_stride,
                                                                       const float *__restrict__ qboxes, long long qboxes_stride, int n,
@@ -44,10 +39,10 @@ __global__ void __launch_bounds__(256) bbox3d_overlaps_aligned_kernel(const floa
     // height and volume composition (bbox3d_iou_calculator.py:140-163)
     const float up = (float)(1.0 - (double)z_center);     // the Python scalar (1 - z_center), rounded to the tensor's fp32
     const float bz = b[z_axis], bh = b[z_axis + 3], qz = q[z_axis], qh = q[z_axis + 3];
-    const float min_z = iou3d_min(bz + bh * up, qz + qh * up);
+    const float min_z = nan_min(bz + bh * up, qz + qh * up);
     const float bt = bz - bh * z_center, qt = qz - qh * z_center;
-    const float max_z = geometric ? iou3d_max(bt, qt) : iou3d_min(bt, qt);
-    const float iw = iou3d_clamp_lo(min_z - max_z, 0.0f);
+    const float max_z = geometric ? nan_max(bt, qt) : nan_min(bt, qt);
+    const float iw = clamp_lo(min_z - max_z, 0.0f);
     const float v1 = b[3] * b[4] * b[5], v2 = q[3] * q[4] * q[5];
     const float inc = iw * rinc;
     float ua;
@@ -55,7 +50,7 @@ __global__ void __launch_bounds__(256) bbox3d_overlaps_aligned_kernel(const floa
     else if (criterion == 0) ua = v1;
     else if (criterion == 1) ua = v2;
     else ua = 1.0f;
-    const float r = inc / iou3d_clamp_lo(ua, 1e-6f);
-    iou[i] = iou3d_clamp_hi(iou3d_clamp_lo(r, 0.0f), 1.0f);
+    const float r = inc / clamp_lo(ua, 1e-6f);
+    iou[i] = clamp_hi(clamp_lo(r, 0.0f), 1.0f);
     if (rinc_out) rinc_out[i] = rinc;
 }

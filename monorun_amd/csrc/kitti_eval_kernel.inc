@@ -18,6 +18,11 @@ __device__ __forceinline__ float t_max(float a, float b) { return fmaxf(a, b); }
 __device__ __forceinline__ double t_max(double a, double b) { return fmax(a, b); }
 __device__ __forceinline__ float t_min(float a, float b) { return fminf(a, b); }
 __device__ __forceinline__ double t_min(double a, double b) { return fmin(a, b); }
+// torch's / numpy's element-wise forms, which keep a NaN where fminf / fmaxf drop it (the 3-D IoU, the projection loss, the score head)
+__device__ __forceinline__ float nan_min(float a, float b) { return (a != a || a < b) ? a : b; }       // torch.min / np.minimum: NaN from either side
+__device__ __forceinline__ float nan_max(float a, float b) { return (a != a || a > b) ? a : b; }       // np.maximum
+__device__ __forceinline__ float clamp_lo(float x, float lo) { return x < lo ? lo : x; }               // clamp(min=lo); torch.relu is clamp_lo(x, 0): NaN stays
+__device__ __forceinline__ float clamp_hi(float x, float hi) { return x > hi ? hi : x; }               // clamp(max=hi), NaN stays
 
 // a*b + c*d rounded operation by operation, never fused into an FMA
 template <typename T>
@@ -26,7 +31,9 @@ __device__ __forceinline__ T dot2_unfused(T a, T b, T c, T d) {
     return a * b + c * d;
 }
 
-// Cyrus-Beck clipped boundary integral (see edge_inside_area above), any scalar type.  UNFUSED (the 3-D IoU, iou3d_kernel.inc): the
+// length-weighted boundary integral of the part of segment p->p+d that lies inside the convex CCW polygon q
+// (Cyrus-Beck parametric clipping, no dynamic arrays); CLOSED selects >= (boundary counts) or > (it does not),
+// so that an edge shared by both rectangles is counted exactly once.  Any scalar type (float: the NMS).  UNFUSED (the 3-D IoU, iou3d_kernel.inc): the
 // two dot products are not contracted, so that an edge lying on the other box's edge (identical boxes) gives den == 0 and f0 == 0
 // exactly and the shared edge is counted once; the default (the KITTI evaluator) compiles as it always has.
 template <typename T, bool CLOSED, bool UNFUSED = false>
@@ -36,7 +43,7 @@ __device__ __forceinline__ T edge_inside_area_t(T px, T py, T dx, T dy, const T 
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const T ax = qx[e], ay = qy[e], bx = qx[(e + 1) & 3], by = qy[(e + 1) & 3];
-        const T nx = -(by - ay), ny = bx - ax;
+        const T nx = -(by - ay), ny = bx - ax;                      // inward normal of a CCW edge
         T f0, den;
         if constexpr (UNFUSED) { f0 = dot2_unfused(nx, px - ax, ny, py - ay); den = dot2_unfused(nx, dx, ny, dy); }
         else { f0 = nx * (px - ax) + ny * (py - ay); den = nx * dx + ny * dy; }

@@ -39,10 +39,7 @@ constexpr int kWpo6 = 4, kThreads6 = 64 * kWpo6;      // waves per object.  Meas
                                                       // Round 5: the LM's H / g lane-packed (Eval6), the rotation, the iterate and the scaling in scalar registers:
                                                       // 219 VGPRs + 104 SGPR spills -> 163 + 58, three waves per SIMD without scratch; 99.1 -> 89.9 us per 1024 objects,
                                                       // the 17-iteration object alone 69 -> 65 us (outputs unchanged).
-__device__ __forceinline__ constexpr int tri6(int i, int j) {        // packed upper triangle, row-major
-    const int a = i <= j ? i : j, b = i <= j ? j : i;
-    return a * 6 - a * (a - 1) / 2 + (b - a);
-}
+__device__ __forceinline__ constexpr int tri6(int i, int j) { return tri_index<6>(i, j); }        // packed upper triangle, row-major
 
 struct Rot6 { double R[9]; double D[9]; bool small; };             // D: columns j_k of J_l(r) (row-major 3x3), unused when small
 

@@ -343,9 +343,16 @@ __device__ __forceinline__ void chol_substitute(const double (&L)[n * n], const 
 // 4x4 SPD factorisation with reciprocal pivots (LM step / covariance; tolerance-level parity only).
 // Symmetric 4x4 matrices are kept as their 10 unique entries, index sym4(i,j) with i >= j:
 //   (0,0)=0 (1,0)=1 (2,0)=2 (3,0)=3 (1,1)=4 (2,1)=5 (3,1)=6 (2,2)=7 (3,2)=8 (3,3)=9
+// (own text although it equals tri_index<4>: written through tri_index it moves the code of pnp_uncert_kernel)
 __device__ __forceinline__ constexpr int sym4(int i, int j) {
     const int a = i >= j ? i : j, b = i >= j ? j : i;
     return b == 0 ? a : b == 1 ? 3 + a : b == 2 ? 5 + a : 9;
+}
+// the packed triangle of a symmetric N x N matrix, row-major from the diagonal on (tri6 of pnp6_kernel.inc, tri7 of pnp_noc_kernel.inc)
+template <int N>
+__device__ __forceinline__ constexpr int tri_index(int i, int j) {
+    const int a = i <= j ? i : j, b = i <= j ? j : i;
+    return a * N - a * (a - 1) / 2 + (b - a);
 }
 struct Chol4 { double L[10]; double inv[4]; bool ok; };
 // factor A = diag(sc) H diag(sc) + diag(d)   (sc = nullptr-like all-ones when SCALED is false)

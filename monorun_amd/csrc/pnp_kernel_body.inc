@@ -135,6 +135,7 @@
 
     // ---------------------------------------------------------------- stage 1: istd inlier mask (R4) + candidate list
     // Three barriers in all: after the sums, after the ballots, after the list.
+    // (own text, repeated in istd_mask_stage and pnp6_refine_kernel: as shared functions the sums and the list loop move all three kernels' code — HISTORY.md, round 12)
     int n = 0;                                          // number of candidates = entries of slist
     if constexpr (EXT) {
         // the external initialiser's inlier mask IS the candidate set (pnp_uncert_cpu.py:43-51: mask[mask] = ransac_mask); no "> 4" rule here

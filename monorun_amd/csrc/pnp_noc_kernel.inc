@@ -22,10 +22,7 @@ struct NocArgs {
 };
 
 constexpr int kNocAcc = 36;
-__device__ __forceinline__ constexpr int tri7(int i, int j) {        // packed upper triangle, row-major, i <= j after ordering
-    const int a = i <= j ? i : j, b = i <= j ? j : i;
-    return a * 7 - a * (a - 1) / 2 + (b - a);
-}
+__device__ __forceinline__ constexpr int tri7(int i, int j) { return tri_index<7>(i, j); }        // packed upper triangle, row-major, i <= j after ordering
 
 // In-place Cholesky solve of a packed symmetric positive definite N x N system (upper triangle, tri-index order): the
 // factor overwrites `A`, so N(N+1)/2 doubles are live instead of 2 N^2.  Reciprocal pivots from v_rsq_f64 (fast_rsqrt).

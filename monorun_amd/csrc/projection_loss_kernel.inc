@@ -28,9 +28,6 @@ __host__ __device__ inline int robust_kl_blocks(long long numel) {
     return (int)(b < 1 ? 1 : (b > kKlMaxBlocks ? kKlMaxBlocks : b));
 }
 
-__device__ __forceinline__ float proj_clamp_lo(float x, float lo) { return x < lo ? lo : x; }               // clamp(min=lo), NaN stays
-__device__ __forceinline__ float proj_min(float a, float b) { return (a != a || a < b) ? a : b; }           // torch.min, NaN from either side
-
 struct ProjSetup { float pr[9], pt[3], umax, vmax; };
 
 // Per-object P_R = K @ R_y(yaw), P_t = K @ t and the upper clamp bounds [W, H] + border.
@@ -66,10 +63,10 @@ __global__ void __launch_bounds__(256) uncert_projection_kernel(const float *__r
     const float pu = s.pr[0] * X + s.pr[1] * Y + s.pr[2] * Z + s.pt[0];
     const float pv = s.pr[3] * X + s.pr[4] * Y + s.pr[5] * Z + s.pt[1];
     const float pz = s.pr[6] * X + s.pr[7] * Y + s.pr[8] * Z + s.pt[2];
-    const float zc = proj_clamp_lo(pz, z_min);
+    const float zc = clamp_lo(pz, z_min);
     float *out = c2d + o * 2 * hw + px;
-    out[0] = proj_min(proj_clamp_lo(pu / zc, -border), s.umax);
-    out[hw] = proj_min(proj_clamp_lo(pv / zc, -border), s.vmax);
+    out[0] = nan_min(clamp_lo(pu / zc, -border), s.umax);
+    out[hw] = nan_min(clamp_lo(pv / zc, -border), s.vmax);
 }
 
 __global__ void __launch_bounds__(256) uncert_projection_backward_kernel(const float *__restrict__ c3d, const float *__restrict__ pose,
@@ -86,14 +83,14 @@ __global__ void __launch_bounds__(256) uncert_projection_backward_kernel(const f
     const float pu = s.pr[0] * X + s.pr[1] * Y + s.pr[2] * Z + s.pt[0];
     const float pv = s.pr[3] * X + s.pr[4] * Y + s.pr[5] * Z + s.pt[1];
     const float pz = s.pr[6] * X + s.pr[7] * Y + s.pr[8] * Z + s.pt[2];
-    const float zc = proj_clamp_lo(pz, z_min);
+    const float zc = clamp_lo(pz, z_min);
     const float *g = g2d + o * 2 * hw + px;
     float gp[2];
     const float num[2] = { pu, pv }, hi[2] = { s.umax, s.vmax }, gin[2] = { g[0], g[hw] };
     float gz = 0.0f;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-        const float u0 = num[c] / zc, u1 = proj_clamp_lo(u0, -border);
+        const float u0 = num[c] / zc, u1 = clamp_lo(u0, -border);
         // torch.min backward: grad / 2 at a tie, 0 where this side is the larger; then clamp(min) passes at its bound
         float gu = u1 == hi[c] ? gin[c] / 2.0f : (u1 > hi[c] ? 0.0f : gin[c]);
         gu = u0 >= -border ? gu : 0.0f;
@@ -159,7 +156,7 @@ __global__ void __launch_bounds__(256) robust_kl_fold_kernel(const double *__res
         m = m + momentum * avg;
         mean_inv_std[0] = m;
     }
-    const float c = proj_clamp_lo(m, 1e-6f);
+    const float c = clamp_lo(m, 1e-6f);
     double s = a[1] / (double)c;
     if (mean) s = s / (double)numel;
     loss[0] = loss_weight * (float)s;

@@ -42,8 +42,6 @@ struct ScoreArgs {
     const uint8_t *ret_val; const float *scores_2d, *params; int n, c1, c2, sigmoid; float *out;
 };
 
-__device__ __forceinline__ float score_relu(float v) { return v < 0.0f ? 0.0f : v; }          // NaN stays, as torch.relu keeps it
-
 __global__ void __launch_bounds__(kScoreThreads) score_head_forward_kernel(ScoreArgs a) {
     __shared__ __attribute__((aligned(16))) float s_h1[MR_SCORE_MAX_C1 * kScoreRows];
     __shared__ __attribute__((aligned(16))) float s_part[4 * kScoreRows * 256];
@@ -91,7 +89,7 @@ __global__ void __launch_bounds__(kScoreThreads) score_head_forward_kernel(Score
         for (int r = 0; r < kScoreRows; ++r) {
             const long long row = row0 + r;
             const float g = row < a.n ? a.reg[row * a.reg_stride + j] : 0.0f;
-            hp[r] = score_relu(acc[r] + b) + g;
+            hp[r] = clamp_lo(acc[r] + b, 0.0f) + g;
         }
         *reinterpret_cast<float4 *>(&s_h1[j * kScoreRows]) = h;
     }
@@ -133,7 +131,7 @@ __global__ void __launch_bounds__(kScoreThreads) score_head_forward_kernel(Score
             for (int r = 0; r < kScoreRows; ++r) {
                 const float s = ((s_part[(0 * kScoreRows + r) * 256 + tid] + s_part[(1 * kScoreRows + r) * 256 + tid]) +
                                  s_part[(2 * kScoreRows + r) * 256 + tid]) + s_part[(3 * kScoreRows + r) * 256 + tid];
-                dot[r] = fmaf(score_relu(s + b), w3, dot[r]);
+                dot[r] = fmaf(clamp_lo(s + b, 0.0f), w3, dot[r]);
             }
         }
     }

@@ -3,15 +3,12 @@ since round 8 `epnp_refit_betas_kernel` also computes the three candidates' pose
 (`pnp_uncert_refit_kernel`) only their error passes.  The lane-mapped launch must keep two waves per SIMD and no scratch in every
 mapping; the LM launch must keep the occupancy, scratch and (up to the 8-register allocation granule) the registers it had before
 (profiles/r08_kernel_resources.txt).  Needs hipcc, no GPU."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+from tests.kernel_resources import have_hipcc, kernel_resources
+
 
 # pnp_uncert_refit_kernel<T, WPO> before round 8: (VGPRs, waves per SIMD, scratch bytes per lane)
 LM_BEFORE = {('f', 2): (144, 3, 0), ('f', 4): (128, 4, 28), ('f', 8): (128, 4, 20),
@@ -23,24 +20,9 @@ def _alloc(v):
     return (v + 7) // 8 * 8
 
 
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which('hipcc')), reason='hipcc not installed')
+@pytest.mark.skipif(not have_hipcc(), reason='hipcc not installed')
 def test_refit_launches_keep_their_occupancy_and_no_new_scratch():
-    cmd = [HIPCC, '--offload-arch=gfx950', '-O3', '-std=c++17', '-I', os.path.join(ROOT, 'include'), '--cuda-device-only', '-c',
-           '-Rpass-analysis=kernel-resource-usage', os.path.join(ROOT, 'monorun_amd', 'csrc', 'monorun_pnp.hip'), '-o', os.devnull]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r'Function Name: (\S+)', line)
-        if m:
-            cur = m.group(1)
-            kernels[cur] = {}
-            continue
-        for key, pat in (('vgpr', r' VGPRs: (\d+)'), ('spill', r'VGPRs Spill: (\d+)'), ('scratch', r'ScratchSize \[bytes/lane\]: (\d+)'),
-                         ('occ', r'Occupancy \[waves/SIMD\]: (\d+)')):
-            m = re.search(pat, line)
-            if m and cur:
-                kernels[cur][key] = int(m.group(1))
+    kernels = kernel_resources()
     betas = {k: v for k, v in kernels.items() if 'epnp_refit_betas_kernel' in k}
     assert len(betas) == 3, sorted(kernels)                                # LV = 0 | 2 | 4: quad, row, wave
     for name, r in betas.items():
