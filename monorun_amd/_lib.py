@@ -1,5 +1,5 @@
 """ctypes loader / builder for libmonorun_pnp.so (the C ABI declared in include/monorun_pnp.h and, for the head kernels behind the
-PnP, include/monorun_heads.h).
+PnP, include/monorun_heads.h, and for the training decode, include/monorun_train.h).
 
 The library is built in-tree by hipcc for gfx950 (``build()``; also driven by
 ``__graft_entry__.build()``) and loaded with ctypes — cffi, which the reference uses
@@ -18,6 +18,7 @@ SRC = os.path.join(_HERE, 'csrc', 'monorun_pnp.hip')
 INCLUDE = os.path.join(_ROOT, 'include')
 HEADER = os.path.join(INCLUDE, 'monorun_pnp.h')
 HEADS_HEADER = os.path.join(INCLUDE, 'monorun_heads.h')      # the head kernels' entry points: same library, a header of their own
+TRAIN_HEADER = os.path.join(INCLUDE, 'monorun_train.h')      # the training decode's entry points: likewise
 SO = os.environ.get('MR_PNP_SO') or os.path.join(_HERE, 'libmonorun_pnp.so')     # MR_PNP_SO: A/B-test another build of the library
 
 MR_F32, MR_F16, MR_F64, MR_BF16 = 0, 1, 2, 3
@@ -42,7 +43,7 @@ def _stale():
         return True
     t = os.path.getmtime(SO)
     csrc = os.path.join(_HERE, 'csrc')
-    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER, HEADS_HEADER]
+    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER, HEADS_HEADER, TRAIN_HEADER]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -88,12 +89,12 @@ def _ctype(name, ctype):
 
 def _prototype(fn):
     """(restype, [argtypes], (argument names without the trailing stream), (names of the per-call pointer tables `T *const *`),
-    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h or include/monorun_heads.h declares it.  The headers
+    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h, include/monorun_heads.h or include/monorun_train.h declares it.  The headers
     are read once."""
     global _prototypes
     if _prototypes is None:
         protos = {}
-        for name, ret, args in header_prototypes() + header_prototypes(HEADS_HEADER):
+        for name, ret, args in header_prototypes() + header_prototypes(HEADS_HEADER) + header_prototypes(TRAIN_HEADER):
             if not name.startswith('mr_'):
                 continue                                # the reference's cffi symbols of ext.h: declared by hand in load()
             assert name not in protos, f'{name}: declared twice'
@@ -137,7 +138,7 @@ def ptr(t):
 
 def load():
     """Return the ctypes handle; raises if the library has not been built.  restype / argtypes of every `mr_*` entry point come
-    from its prototype in include/monorun_pnp.h or include/monorun_heads.h (``_prototype``)."""
+    from its prototype in include/monorun_pnp.h, include/monorun_heads.h or include/monorun_train.h (``_prototype``)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -147,7 +148,7 @@ def load():
             '(hipcc --offload-arch=gfx950). monorun_amd has no CPU fallback.')
     lib = ctypes.CDLL(SO)
     vp, i32 = ctypes.c_void_p, ctypes.c_int
-    for name, _, _ in header_prototypes() + header_prototypes(HEADS_HEADER):
+    for name, _, _ in header_prototypes() + header_prototypes(HEADS_HEADER) + header_prototypes(TRAIN_HEADER):
         if name.startswith('mr_'):
             f = getattr(lib, name)
             f.restype, argtypes = _prototype(name)[:2]
@@ -182,3 +183,5 @@ EXPORTED_SYMBOLS = ('mr_pnp_version', 'mr_spin', 'mr_pick_waves', 'mr_pnp_error_
                     'mr_kitti_overlaps', 'mr_kitti_match_workspace_bytes', 'mr_kitti_match', 'mr_roi_align_avg')
 # the entry points of include/monorun_heads.h: the same library, outside the cffi surface of monorun_pnp.h
 HEADS_EXPORTED_SYMBOLS = ('mr_score_head_forward',)
+# the entry points of include/monorun_train.h (the NOC head's training decode): the same library again
+TRAIN_EXPORTED_SYMBOLS = ('mr_noc_decode_train', 'mr_noc_decode_train_backward')

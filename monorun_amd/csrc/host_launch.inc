@@ -343,6 +343,21 @@ int launch_epnp_stages(EpnpStageArgs &ea, void *workspace, size_t workspace_byte
     return rc;
 }
 
+// N8, the training decode (noc_decode_train_kernel.inc): the forward with a thread per RoI pixel, (h w + 255) / 256 workgroups per object as the
+// scalar K2 kernel; the backward with a workgroup per object
+int launch_noc_decode_train(const DecodeTrainArgs &t, hipStream_t st) {
+    unsigned blocks;
+    if (grid_1d((long long)((t.d.h * t.d.w + 255) / 256) * t.d.B, 1, blocks) != MR_OK) return MR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(noc_decode_train_kernel, dim3(blocks), dim3(256), 0, st, t);
+    HIP_TRY(hipGetLastError());
+    return MR_OK;
+}
+int launch_noc_decode_train_backward(const DecodeTrainArgs &t, hipStream_t st) {
+    hipLaunchKernelGGL(noc_decode_train_backward_kernel, dim3((unsigned)t.d.B), dim3(256), 0, st, t);
+    HIP_TRY(hipGetLastError());
+    return MR_OK;
+}
+
 // The correspondence inputs of the per-object launches as the C ABI passes them: x2d / istd / x3d with their (b, p, c) element strides, the
 // fp32 camera matrices and u / v clip ranges (a batch of 1 is broadcast to every object).
 struct CorrIn {

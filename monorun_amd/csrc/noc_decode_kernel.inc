@@ -116,6 +116,8 @@ __device__ __forceinline__ float pred_at(const DecodeArgs &a, long long i) {
     return __uint_as_float((unsigned)((const unsigned short *)a.all_pred)[i] << 16);            // bfloat16
 }
 
+// WITH_ROI = false: the class / flip channel pick and the dim decode only — what the training decode needs (noc_decode_train_kernel.inc); a.rois is not read
+template <bool WITH_ROI = true>
 __device__ __forceinline__ void decode_object(const DecodeArgs &a, int b, DecodeObj &o) {
 #pragma clang fp contract(off)
     const int hw = a.h * a.w;
@@ -130,6 +132,7 @@ __device__ __forceinline__ void decode_object(const DecodeArgs &a, int b, Decode
         o.dv[k] = a.has_var ? a.dim_var[b * 3 + k] * (sd * sd) : 0.0f;
         o.nm[k] = a.noc_means[k]; o.ns[k] = a.noc_stds[k];
     }
+    if constexpr (WITH_ROI) {
     const float x1 = a.rois[b * 4 + 0], y1 = a.rois[b * 4 + 1], x2 = a.rois[b * 4 + 2], y2 = a.rois[b * 4 + 3];
     o.x1 = x1; o.y1 = y1;
     o.su = (x2 - x1) / (float)a.w; o.sv = (y2 - y1) / (float)a.h;
@@ -143,6 +146,7 @@ __device__ __forceinline__ void decode_object(const DecodeArgs &a, int b, Decode
         v_last = (y1 - 0.5f) + ((float)(a.h - 1) + 0.5f) * o.sv; v_first = (y1 - 0.5f) + 0.5f * o.sv;
     }
     o.thr = a.ratio * (v_last - v_first);
+    }
     o.base = (long long)b * (2 * Cn * 5) * hw;
     o.ch_noc = f * 5 * Cn + 3 * c; o.ch_ls = f * 5 * Cn + 3 * Cn + 2 * c;
 }
