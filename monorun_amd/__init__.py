@@ -2,7 +2,7 @@
 
 Drop-in surface: ``monorun_amd.ops`` mirrors the reference's ``monorun.ops``
 (build_pnp / PnPUncert / pnp_uncert / u2d_pnp_cpu / PNP).  Around it: ``pose_head`` (NOC-head decode, pose head mirror,
-fused head -> pose launch, RoIAlign), ``noc_head`` (the NOC head's training decode), ``consumers`` (3-D box packing, rotated-BEV NMS), ``evaluation`` (KITTI evaluator and
+fused head -> pose launch, RoIAlign), ``noc_head`` (the NOC head's training decode, targets and loss), ``noc_targets`` (its dense LiDAR targets), ``consumers`` (3-D box packing, rotated-BEV NMS), ``evaluation`` (KITTI evaluator and
 wire format), ``parallel`` (object sharding, RCCL exchange), ``synthetic`` (seeded workloads).  See DESIGN.md and INTEGRATION.md.
 """
 from . import _lib  # noqa: F401

@@ -1,5 +1,6 @@
 """ctypes loader / builder for libmonorun_pnp.so (the C ABI declared in include/monorun_pnp.h and, for the head kernels behind the
-PnP, include/monorun_heads.h, and for the training decode, include/monorun_train.h).
+PnP, include/monorun_heads.h, for the training decode, include/monorun_train.h, and for the NOC targets and loss_noc,
+include/monorun_targets.h).
 
 The library is built in-tree by hipcc for gfx950 (``build()``; also driven by
 ``__graft_entry__.build()``) and loaded with ctypes — cffi, which the reference uses
@@ -19,6 +20,7 @@ INCLUDE = os.path.join(_ROOT, 'include')
 HEADER = os.path.join(INCLUDE, 'monorun_pnp.h')
 HEADS_HEADER = os.path.join(INCLUDE, 'monorun_heads.h')      # the head kernels' entry points: same library, a header of their own
 TRAIN_HEADER = os.path.join(INCLUDE, 'monorun_train.h')      # the training decode's entry points: likewise
+TARGETS_HEADER = os.path.join(INCLUDE, 'monorun_targets.h')  # the dense NOC targets' and loss_noc's entry points: likewise
 SO = os.environ.get('MR_PNP_SO') or os.path.join(_HERE, 'libmonorun_pnp.so')     # MR_PNP_SO: A/B-test another build of the library
 
 MR_F32, MR_F16, MR_F64, MR_BF16 = 0, 1, 2, 3
@@ -43,7 +45,7 @@ def _stale():
         return True
     t = os.path.getmtime(SO)
     csrc = os.path.join(_HERE, 'csrc')
-    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER, HEADS_HEADER, TRAIN_HEADER]
+    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER, HEADS_HEADER, TRAIN_HEADER, TARGETS_HEADER]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -74,6 +76,10 @@ def header_prototypes(path=HEADER):
     return out
 
 
+def _all_prototypes():
+    return header_prototypes() + header_prototypes(HEADS_HEADER) + header_prototypes(TRAIN_HEADER) + header_prototypes(TARGETS_HEADER)
+
+
 _CTYPES = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64}
 _prototypes = None
 
@@ -89,12 +95,12 @@ def _ctype(name, ctype):
 
 def _prototype(fn):
     """(restype, [argtypes], (argument names without the trailing stream), (names of the per-call pointer tables `T *const *`),
-    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h, include/monorun_heads.h or include/monorun_train.h declares it.  The headers
+    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h, include/monorun_heads.h, include/monorun_train.h or include/monorun_targets.h declares it.  The headers
     are read once."""
     global _prototypes
     if _prototypes is None:
         protos = {}
-        for name, ret, args in header_prototypes() + header_prototypes(HEADS_HEADER) + header_prototypes(TRAIN_HEADER):
+        for name, ret, args in _all_prototypes():
             if not name.startswith('mr_'):
                 continue                                # the reference's cffi symbols of ext.h: declared by hand in load()
             assert name not in protos, f'{name}: declared twice'
@@ -138,7 +144,7 @@ def ptr(t):
 
 def load():
     """Return the ctypes handle; raises if the library has not been built.  restype / argtypes of every `mr_*` entry point come
-    from its prototype in include/monorun_pnp.h, include/monorun_heads.h or include/monorun_train.h (``_prototype``)."""
+    from its prototype in include/monorun_pnp.h, include/monorun_heads.h, include/monorun_train.h or include/monorun_targets.h (``_prototype``)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -148,7 +154,7 @@ def load():
             '(hipcc --offload-arch=gfx950). monorun_amd has no CPU fallback.')
     lib = ctypes.CDLL(SO)
     vp, i32 = ctypes.c_void_p, ctypes.c_int
-    for name, _, _ in header_prototypes() + header_prototypes(HEADS_HEADER) + header_prototypes(TRAIN_HEADER):
+    for name, _, _ in _all_prototypes():
         if name.startswith('mr_'):
             f = getattr(lib, name)
             f.restype, argtypes = _prototype(name)[:2]
@@ -185,3 +191,5 @@ EXPORTED_SYMBOLS = ('mr_pnp_version', 'mr_spin', 'mr_pick_waves', 'mr_pnp_error_
 HEADS_EXPORTED_SYMBOLS = ('mr_score_head_forward',)
 # the entry points of include/monorun_train.h (the NOC head's training decode): the same library again
 TRAIN_EXPORTED_SYMBOLS = ('mr_noc_decode_train', 'mr_noc_decode_train_backward')
+# the entry points of include/monorun_targets.h (the dense NOC targets and loss_noc): the same library again
+TARGETS_EXPORTED_SYMBOLS = ('mr_noc_dense_target', 'mr_smooth_l1_mod_workspace_bytes', 'mr_smooth_l1_mod_loss', 'mr_smooth_l1_mod_loss_backward')

@@ -14,6 +14,9 @@ trains the NOC head in the shipped configs with ``loss_noc=None``.  Its reduced 
 
 ``CrossEntropyLoss`` is the sigmoid form of mmdet's loss of that name, the score head's ``loss_score``, in torch.
 
+``SmoothL1LossMod`` is the NOC head's ``loss_noc`` of the LiDAR-supervised configs, the reference's
+monorun/models/losses/smooth_l1_loss.py.  Its reduced forms on CUDA run HIP kernels; the rest runs in torch.
+
 ``build_loss`` builds a loss config dict: with mmdet's registry when mmdet imports and knows the type, else with this module's
 registry.  A type neither knows becomes an ``UnbuiltLoss``, which raises, naming the type, only when it is called.
 """
@@ -187,6 +190,123 @@ class RobustKLLoss(nn.Module):
         return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# SmoothL1LossMod: the NOC head's loss_noc, the reference's monorun/models/losses/smooth_l1_loss.py.
+
+def smooth_l1_loss_mod(pred, target, beta=1.0):
+    """The per-element loss of ``SmoothL1LossMod``: with the distance d between pred and target, half a parabola 0.5 d d / beta below
+    beta and the line d - 0.5 beta from there on.  target: a tensor of pred's shape, or the integer 0 (pred is the signed error) or -1
+    (pred is the distance itself, taken as given)."""
+    if not beta > 0:
+        raise ValueError(f'smooth_l1_loss_mod: beta must be positive, not {beta}')
+    if isinstance(target, int):
+        if target not in (0, -1):
+            raise ValueError(f'smooth_l1_loss_mod: an integer target must be 0 or -1, not {target}')
+        distance = pred if target == -1 else pred.abs()
+    else:
+        if target.shape != pred.shape or target.numel() == 0:
+            raise ValueError('smooth_l1_loss_mod: pred and target must have the same non-empty shape')
+        distance = (pred - target).abs()
+    parabola = 0.5 * distance * distance / beta
+    line = distance - 0.5 * beta
+    return torch.where(distance < beta, parabola, line)
+
+
+class _SmoothL1ModFunction(torch.autograd.Function):
+    """Reduced loss in two HIP launches (``mr_smooth_l1_mod_loss``), the gradient to pred in one (``mr_smooth_l1_mod_loss_backward``).
+    pred, target and weight arrive as contiguous fp32; target and weight get no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, weight_mode, channels, hw, beta, reduction, loss_weight):
+        from . import _lib
+        lib = _lib.load()
+        numel = pred.numel()
+        dev = pred.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        ws = torch.empty(int(lib.mr_smooth_l1_mod_workspace_bytes(numel)), device=dev, dtype=torch.uint8)
+        ctx.common = dict(pred=pred.data_ptr(), target=target.data_ptr(), weight=_lib.ptr(weight), weight_mode=weight_mode, numel=numel,
+                          channels=channels, hw=hw, beta=beta, reduction=reduction, loss_weight=loss_weight)
+        with torch.cuda.device(dev):
+            _lib.check(lib.mr_smooth_l1_mod_loss(*_lib.pack('mr_smooth_l1_mod_loss', ctx.common, loss=loss.data_ptr(), workspace=ws.data_ptr(),
+                                                            workspace_bytes=ws.numel()), torch.cuda.current_stream(dev).cuda_stream))
+        ctx.save_for_backward(pred, target, weight)
+        ctx.args = (beta, reduction, loss_weight)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import _lib
+        pred, target, weight = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            # create_graph=True: the gradient must carry a graph itself, which the kernel cannot give: torch differentiates the restatement
+            beta, reduction, loss_weight = ctx.args
+            with torch.enable_grad():
+                loss = loss_weight * weight_reduce_loss(smooth_l1_loss_mod(pred, target, beta), weight, 'mean' if reduction == 0 else 'sum')
+                gp, = torch.autograd.grad(loss, pred, grad, create_graph=True)
+            return (gp,) + (None,) * 8
+        grad = grad.to(torch.float32).contiguous()
+        gp = torch.empty_like(pred)
+        dev = pred.device
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().mr_smooth_l1_mod_loss_backward(*_lib.pack('mr_smooth_l1_mod_loss_backward', ctx.common, grad_loss=grad.data_ptr(),
+                                                                             grad_pred=gp.data_ptr()), torch.cuda.current_stream(dev).cuda_stream))
+        return (gp,) + (None,) * 8
+
+
+def _smooth_l1_weight_mode(pred, weight):
+    """0 no weight, 1 of pred's shape, 2 (n, 1, h, w) against a 4-D pred; None: a form the kernels do not take."""
+    if weight is None:
+        return 0
+    if not isinstance(weight, torch.Tensor) or weight.device != pred.device or weight.dtype != torch.float32:
+        return None
+    if weight.shape == pred.shape:
+        return 1
+    if pred.dim() == 4 and weight.shape == (pred.shape[0], 1) + tuple(pred.shape[2:]):
+        return 2
+    return None
+
+
+def _smooth_l1_hip_ok(pred, target, weight, avg_factor, reduction):
+    if avg_factor is not None or reduction not in ('mean', 'sum'):
+        return False
+    if not (isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor)) or pred.device.type != 'cuda':
+        return False
+    if pred.dtype != torch.float32 or target.dtype != torch.float32 or target.device != pred.device:
+        return False
+    if target.shape != pred.shape or pred.numel() == 0:
+        return False
+    return _smooth_l1_weight_mode(pred, weight) is not None
+
+
+class SmoothL1LossMod(nn.Module):
+    """The reference's SmoothL1LossMod: same constructor and call forms.  CUDA fp32 ``pred`` and tensor ``target`` of its shape, with
+    reduction 'mean' or 'sum', no ``avg_factor`` and a weight that is None, of pred's shape or (n, 1, h, w), run the HIP kernels (fp64
+    sum, bitwise reproducible); everything else — integer targets, 'none', ``avg_factor``, CPU or empty inputs, a backward under
+    ``create_graph=True`` — runs :func:`smooth_l1_loss_mod` in torch."""
+
+    def __init__(self, beta=1.0, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.beta = beta
+        self.reduction = reduction
+        self.loss_weight = loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kwargs):
+        if reduction_override not in (None, 'none', 'mean', 'sum'):
+            raise ValueError(f'SmoothL1LossMod: reduction_override {reduction_override!r}')
+        if kwargs:
+            raise TypeError(f'SmoothL1LossMod: unexpected arguments {sorted(kwargs)}')
+        reduction = reduction_override if reduction_override else self.reduction
+        if _smooth_l1_hip_ok(pred, target, weight, avg_factor, reduction):
+            if not self.beta > 0:
+                raise ValueError(f'SmoothL1LossMod: beta must be positive, not {self.beta}')
+            mode = _smooth_l1_weight_mode(pred, weight)
+            channels, hw = (pred.shape[1], pred.shape[2] * pred.shape[3]) if mode == 2 else (1, 1)
+            return _SmoothL1ModFunction.apply(pred.contiguous(), target.detach().contiguous(), weight.detach().contiguous() if mode else None,
+                                              mode, int(channels), int(hw), float(self.beta), 0 if reduction == 'mean' else 1,
+                                              float(self.loss_weight))
+        return self.loss_weight * weight_reduce_loss(smooth_l1_loss_mod(pred, target, beta=self.beta), weight, reduction, avg_factor)
+
+
 class CrossEntropyLoss(nn.Module):
     """The sigmoid form of mmdet's ``CrossEntropyLoss`` (``use_sigmoid=True``), the score head's default ``loss_score``:
     ``binary_cross_entropy_with_logits(pred, target)`` per element, then :func:`weight_reduce_loss`.  ``weight`` is per sample:
@@ -211,7 +331,7 @@ class CrossEntropyLoss(nn.Module):
         return self.loss_weight * weight_reduce_loss(loss, weight, reduction, avg_factor)
 
 
-LOSSES = {'KLLossMV': KLLossMV, 'RobustKLLoss': RobustKLLoss, 'CrossEntropyLoss': CrossEntropyLoss}
+LOSSES = {'KLLossMV': KLLossMV, 'RobustKLLoss': RobustKLLoss, 'CrossEntropyLoss': CrossEntropyLoss, 'SmoothL1LossMod': SmoothL1LossMod}
 
 
 class UnbuiltLoss:

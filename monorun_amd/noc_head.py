@@ -13,10 +13,14 @@ log-std.  :func:`decode_for_training` is differentiable in ``all_pred``, ``dim``
 Hot path: CUDA inputs run one HIP launch forward (``mr_noc_decode_train``) and one backward (``mr_noc_decode_train_backward``, which
 recomputes the forward from the inputs and writes every channel of ``grad_all_pred``).  Everything else — CPU tensors, no objects,
 ``distances`` that require grad, a backward under ``create_graph=True`` — runs :func:`decode_for_training_torch`, the torch restatement.
+
+:func:`get_targets` and :func:`loss` (N9) are the head's LiDAR supervision, ``FCNNOCDecoder.get_targets`` and ``.loss``
+(fcn_noc_decoder.py:269-297): the dense NOC targets by :func:`monorun_amd.noc_targets.noc_targets` and ``loss_noc``.
 """
 import torch
 
 from . import _lib
+from . import noc_targets as _noc_targets
 from .pose_head import DIM_MEANS, DIM_STDS, NOC_MEANS, NOC_STDS, _PRED_DTYPES, _const, _flip_flags
 from .projection_head import DistanceInvarProjErrorCoder
 
@@ -189,3 +193,58 @@ def decode_for_training(all_pred, labels, flip, dim, dim_var=None, distances=Non
     if all_pred.dtype not in _PRED_DTYPES:
         out = {k: v.to(all_pred.dtype) if v is not None else None for k, v in out.items()}
     return out
+
+
+class NOCCoder:
+    """The reference's ``NOCCoder`` (core/bbox_3d/coord_coder/noc_coder.py): ``encode`` of the ground truth's masked coordinate maps into
+    the head's targets, ``decode`` of its predictions into object coordinates and their variance."""
+
+    def __init__(self, target_means=NOC_MEANS, target_stds=NOC_STDS, eps=1e-5):
+        self.target_means = target_means
+        self.target_stds = target_stds
+        self.eps = eps
+
+    def encode(self, gt_coords_3d, gt_coords_3d_mask, dimensions, flip):
+        return _noc_targets.noc_encode(gt_coords_3d, gt_coords_3d_mask, dimensions, flip, self.target_means, self.target_stds, self.eps)
+
+    def decode(self, part, part_var, dimensions, dimensions_var, flip=None):
+        """Encoded parts (n, 3, h, w) and object dimensions (n, 3) -> object coordinates: p = part * std + mean, coords_3d = p * dim.
+        With a variance of the parts and / or of the dimensions (either may be None), the variance of that product of two
+        independent factors: var_p dim^2 + var_dim p^2 + var_p var_dim, var_p = part_var * std^2; None when neither is given.
+        ``flip`` is unused (the reference's decode ignores it too)."""
+        scale = part.new_tensor(self.target_stds)[:, None, None]
+        p = part * scale + part.new_tensor(self.target_means)[:, None, None]
+        extent = dimensions[..., None, None]
+        var_p = part_var * scale.square() if part_var is not None else None
+        var_d = dimensions_var[..., None, None] if dimensions_var is not None else None
+        terms = []
+        if var_p is not None:
+            terms.append(var_p * extent.square())
+        if var_d is not None:
+            terms.append(var_d * p.square())
+        if var_p is not None and var_d is not None:
+            terms.append(var_p * var_d)
+        return p * extent, (sum(terms[1:], terms[0]) if terms else None)
+
+
+def get_targets(sampling_results, gt_coords_3d, gt_coords_3d_mask, gt_bboxes_3d, rcnn_train_cfg, img_metas, coord_coder=None):
+    """``FCNNOCDecoder.get_targets``: per image the sampling result (``pos_bboxes``, ``pos_assigned_gt_inds``), the ground truth's masked
+    coordinate maps and masks, its 3-D boxes (the first three columns are the dimensions) and the image meta (``flip``);
+    ``rcnn_train_cfg.dense_size``.  Returns (noc_targets (n, 3, h, w), noc_weights (n, 1, h, w)) over the positives of the batch."""
+    dense_size = rcnn_train_cfg['dense_size'] if isinstance(rcnn_train_cfg, dict) else rcnn_train_cfg.dense_size
+    return _noc_targets.noc_targets(
+        [res.pos_bboxes for res in sampling_results], [res.pos_assigned_gt_inds for res in sampling_results], gt_coords_3d,
+        gt_coords_3d_mask, [b[:, :3] for b in gt_bboxes_3d], [meta['flip'] for meta in img_metas], dense_size,
+        coord_coder=coord_coder if coord_coder is not None else NOCCoder())
+
+
+def loss(noc_pred, noc_targets, noc_weights, loss_noc):
+    """``FCNNOCDecoder.loss``: dict(loss_noc=...) or, without a ``loss_noc``, an empty dict.  noc_pred is taken in fp32 (the
+    reference's ``force_fp32``); with no positives the loss is ``noc_pred.sum()``, a zero that keeps the graph."""
+    if loss_noc is None:
+        return dict()
+    if noc_pred.dtype in (torch.float16, torch.bfloat16):
+        noc_pred = noc_pred.float()
+    if noc_pred.size(0) == 0:
+        return dict(loss_noc=noc_pred.sum())
+    return dict(loss_noc=loss_noc(noc_pred, noc_targets, weight=noc_weights))
