@@ -269,6 +269,12 @@ int mr_cov_symeig_rule(uint8_t *valid, float *cov, int B, float *eig_min_max, vo
  * inlier_mask (B,P) u8, pose4 (B,4) f32, valid4 (B) u8 = outputs of that call.  Outputs: valid (B) u8, pose6 (B,6) f32,
  * cov6 (B,36) f32 (identity when invalid), diag (B,2) f32 [LM iterations, exit reason as MR_DIAG_WHY] or NULL.
  * flags: only the MR_LM_MAXIT bits are read.
+ * An object that never starts — valid4 == 0, or an empty inlier_mask — is invalid with cov6 = identity and diag = (0, 8): MR_DIAG_WHY's
+ * "initialiser failed (no LM run)".  Its pose6 is zero when valid4 == 0 and the start pose (0, yaw, 0, tx, ty, tz) when valid4 != 0.
+ * An evaluation failure (a non-finite cost, gradient or J^T J at the start pose: NaN / Inf in an inlier's data or in pose4) returns the
+ * start pose as well, invalid, cov6 = identity, diag = (0, 7).  An object whose LM ends in five invalid steps (reason 6) or whose J^T J
+ * has no Cholesky factor returns the LM's pose, invalid, cov6 = identity.  With fewer than 3 inliers (2 n < 6 residuals: J^T J is
+ * singular) there is no covariance whatever the rounding of a pivot: the LM's pose and diag, invalid, cov6 = identity.
  */
 int mr_pnp6_refine_batched(
     const void *x2d, const int64_t *x2d_strides, const void *istd, const int64_t *istd_strides,

@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(kThreads6, MR_PNP6_WAVES) pnp6_refine_kernel(c
     cam.vmin = uni(ld_k(a.vr, a.r_f64, ro)); cam.vmax = uni(ld_k(a.vr, a.r_f64, ro + 1));
 
     const int N = 6;
-    const bool start_ok = a.valid4[b] != 0 && n > 0;
+    const bool have4 = a.valid4[b] != 0, start_ok = have4 && n > 0;
     // (the iterate, the returned pose and the Jacobi scaling are wave-uniform: scalar registers)
     double x[6] = { 0.0, uni((double)a.pose4[(long long)b * 4]), 0.0, uni((double)a.pose4[(long long)b * 4 + 1]), uni((double)a.pose4[(long long)b * 4 + 2]),
                     uni((double)a.pose4[(long long)b * 4 + 3]) };
@@ -291,7 +291,7 @@ __global__ void __launch_bounds__(kThreads6, MR_PNP6_WAVES) pnp6_refine_kernel(c
         for (int m = 0; m < N; ++m)
 #pragma unroll
             for (int nn = 0; nn < N; ++nn) A[6 * m + nn] = h6(cur, m, nn);
-        bool inv_ok = chol_factor_fast<6>(A, L, inv);
+        bool inv_ok = chol_factor_fast<6>(A, L, inv) && 2 * n >= N;      // 2 n < 6 residuals: J^T J is singular, whichever way a rounding-level pivot falls
 #pragma unroll
         for (int c = 0; c < N; ++c) {
             double e[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, s[6];
@@ -309,7 +309,7 @@ __global__ void __launch_bounds__(kThreads6, MR_PNP6_WAVES) pnp6_refine_kernel(c
     if (tid == 0) {
         a.valid[b] = valid ? 1 : 0;
 #pragma unroll
-        for (int j = 0; j < N; ++j) a.pose6[(long long)b * 6 + j] = start_ok ? (float)out[j] : 0.0f;
+        for (int j = 0; j < N; ++j) a.pose6[(long long)b * 6 + j] = have4 ? (float)out[j] : 0.0f;      // the start pose unless the LM moved it; zeros only without a 4-DoF result
         if (a.diag) { a.diag[(long long)b * 2] = (float)iteration; a.diag[(long long)b * 2 + 1] = (float)why; }
 #pragma unroll
         for (int i = 0; i < 36; ++i) a.cov6[(long long)b * 36 + i] = (float)cov[i];

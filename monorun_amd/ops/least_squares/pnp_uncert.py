@@ -508,7 +508,12 @@ class PnPPipeline:
 def pnp6_refine_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range, inlier_mask_u8, pose4, valid4_u8, z_min=0.5,
                        flags=0, with_diag=False):
     """Second launch of the 6-DoF mode (``mr_pnp6_refine_batched``): 6-DoF LM from the 4-DoF result on its inlier set.
-    Returns (valid u8 (B,), pose6 f32 (B,6) [rx,ry,rz,tx,ty,tz], cov6 f32 (B,6,6), diag f32 (B,2)|None)."""
+    Returns (valid u8 (B,), pose6 f32 (B,6) [rx,ry,rz,tx,ty,tz], cov6 f32 (B,6,6), diag f32 (B,2)|None); diag = [LM passes, exit reason as
+    MR_DIAG_WHY].  flags: only the MR_LM_MAXIT bits are read.
+    An object that never starts (valid4 == 0, or valid4 != 0 with an empty mask) is invalid with cov6 = identity and diag = (0, 8)
+    ("initialiser failed"); its pose6 is zero when valid4 == 0 and the start pose (0, yaw, 0, t) otherwise.  A non-finite first
+    evaluation (NaN / Inf in an inlier's data or in pose4) returns the start pose too: invalid, cov6 = identity, diag = (0, 7).  Fewer than
+    three inliers never give a covariance (J^T J is singular): the LM's pose, invalid, cov6 = identity."""
     lib = _lib.load()
     dev, B, P, common, _ = _inputs(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v_range)
     f32 = dict(device=dev, dtype=torch.float32)

@@ -401,12 +401,12 @@ def cv_rng_uniform(seed, count, a, b):
 
 
 def pnp6_uncert(pts2d, pts3d, wgt2d, K, init_pose6, clips):
-    """6-DoF solve of one object (host fp64): returns dict(val, pose (6,), cov (6,6), tr, iters, why)."""
+    """6-DoF solve of one object (host fp64): returns dict(val, pose (6,), cov (6,6), tr, iters, why, final_cost, n_success = accepted steps)."""
     pts2d, pts3d, wgt2d, K, init_pose6, clips = map(_d, (pts2d, pts3d, wgt2d, K, init_pose6, clips))
-    val, pose, cov, tr, diag = np.zeros(1, np.int32), np.zeros(6), np.eye(6), np.zeros(1), np.zeros(5)
+    val, pose, cov, tr, diag = np.zeros(1, np.int32), np.zeros(6), np.eye(6), np.zeros(1), np.zeros(6)
     lib().orc_pnp6_uncert(_p(pts2d, c_dp), _p(pts3d, c_dp), _p(wgt2d, c_dp), _p(K, c_dp), _p(init_pose6, c_dp), _p(val, c_ip), _p(pose, c_dp),
                           _p(cov, c_dp), _p(tr, c_dp), ctypes.c_int(pts2d.shape[0]), _p(clips, c_dp), _p(diag, c_dp))
-    return dict(val=int(val[0]), pose=pose, cov=cov, tr=float(tr[0]), iters=int(diag[0]), why=int(diag[1]), final_cost=diag[4])
+    return dict(val=int(val[0]), pose=pose, cov=cov, tr=float(tr[0]), iters=int(diag[0]), why=int(diag[1]), final_cost=diag[4], n_success=int(diag[5]))
 
 
 def eval6(pts2d, pts3d, wgt2d, K, pose6, clips):

@@ -1002,7 +1002,7 @@ static int orc_spd_inverse_n(int n, const double *H, double *inv) {
     for (int i = 0; i < n * n; ++i) if (!isfinite(inv[i])) return 0;
     return 1;
 }
-/* one object, host fp64 buffers (the 6-DoF analogue of ext.h's pnp_uncert); diag: iters, why, termination, init/final cost */
+/* one object, host fp64 buffers (the 6-DoF analogue of ext.h's pnp_uncert); diag (6): iters, why, termination, init/final cost, n_success */
 void orc_pnp6_uncert(double *pts2d, double *pts3d, double *wgt2d, double *K, double *init_pose6, int *result_val, double *result_pose6,
                      double *result_cov36, double *result_tr, int pn, double *clips, double *diag) {
     orc_problem pb;
@@ -1013,10 +1013,11 @@ void orc_pnp6_uncert(double *pts2d, double *pts3d, double *wgt2d, double *K, dou
     orc_lm_n(6, orc_eval6_cb, &pb, init_pose6, result_pose6, &sm);
     *result_val = (sm.termination == ORC_CONVERGENCE || sm.termination == ORC_NO_CONVERGENCE) ? 1 : 0;
     *result_tr = sm.radius;
-    if (diag) { diag[0] = sm.num_iterations; diag[1] = sm.why; diag[2] = sm.termination; diag[3] = sm.initial_cost; diag[4] = sm.final_cost; }
+    if (diag) { diag[0] = sm.num_iterations; diag[1] = sm.why; diag[2] = sm.termination; diag[3] = sm.initial_cost; diag[4] = sm.final_cost; diag[5] = sm.num_successful; }
     if (*result_val && result_cov36) {
         double cost, g[6], H[36], inv[36];
-        int ok = orc_eval6_cb(&pb, result_pose6, &cost, g, H) && orc_spd_inverse_n(6, H, inv);
+        /* fewer than 3 points = fewer than 6 residuals: rank(J^T J) <= 2 pn < 6, no covariance, whichever way a rounding-level pivot falls */
+        int ok = 2 * pn >= 6 && orc_eval6_cb(&pb, result_pose6, &cost, g, H) && orc_spd_inverse_n(6, H, inv);
         *result_val = ok ? 1 : 0;
         if (ok) memcpy(result_cov36, inv, sizeof inv);
     }
@@ -1049,7 +1050,7 @@ void orc_pnp6_refine_batch(const float *x2d, const float *istd, const float *x3d
         const float *Kf = K + (Kb == 1 ? 0 : (size_t)b * 9), *ur = u_range + (Rb == 1 ? 0 : (size_t)b * 2), *vr = v_range + (Rb == 1 ? 0 : (size_t)b * 2);
         double Kd[9]; for (int i = 0; i < 9; ++i) Kd[i] = Kf[i];
         double clips[5] = { z_min, ur[0], ur[1], vr[0], vr[1] };
-        double init[6] = { 0.0, pose4[4 * b], 0.0, pose4[4 * b + 1], pose4[4 * b + 2], pose4[4 * b + 3] }, out[6], cov[36], tr, dg[5] = {0, 0, 0, 0, 0};
+        double init[6] = { 0.0, pose4[4 * b], 0.0, pose4[4 * b + 1], pose4[4 * b + 2], pose4[4 * b + 3] }, out[6], cov[36], tr, dg[6] = {0, 0, 0, 0, 0, 0};
         int val = 0;
         for (int i = 0; i < 36; ++i) cov[i] = (i % 7 == 0) ? 1.0 : 0.0;
         memcpy(out, init, sizeof out);
