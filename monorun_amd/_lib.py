@@ -1,6 +1,7 @@
 """ctypes loader / builder for libmonorun_pnp.so (the C ABI declared in include/monorun_pnp.h and, for the head kernels behind the
 PnP, include/monorun_heads.h, for the training decode, include/monorun_train.h, and for the NOC targets and loss_noc,
-include/monorun_targets.h, and for the global head, include/monorun_global.h).
+include/monorun_targets.h, for the global head, include/monorun_global.h, and for the NOC head trunk's CARAFE upsampler,
+include/monorun_carafe.h).
 
 The library is built in-tree by hipcc for gfx950 (``build()``; also driven by
 ``__graft_entry__.build()``) and loaded with ctypes — cffi, which the reference uses
@@ -22,6 +23,7 @@ HEADS_HEADER = os.path.join(INCLUDE, 'monorun_heads.h')      # the head kernels'
 TRAIN_HEADER = os.path.join(INCLUDE, 'monorun_train.h')      # the training decode's entry points: likewise
 TARGETS_HEADER = os.path.join(INCLUDE, 'monorun_targets.h')  # the dense NOC targets' and loss_noc's entry points: likewise
 GLOBAL_HEADER = os.path.join(INCLUDE, 'monorun_global.h')    # the global head's entry points: likewise
+CARAFE_HEADER = os.path.join(INCLUDE, 'monorun_carafe.h')    # the CARAFE upsampler's entry points: likewise
 SO = os.environ.get('MR_PNP_SO') or os.path.join(_HERE, 'libmonorun_pnp.so')     # MR_PNP_SO: A/B-test another build of the library
 
 MR_F32, MR_F16, MR_F64, MR_BF16 = 0, 1, 2, 3
@@ -46,7 +48,7 @@ def _stale():
         return True
     t = os.path.getmtime(SO)
     csrc = os.path.join(_HERE, 'csrc')
-    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER, HEADS_HEADER, TRAIN_HEADER, TARGETS_HEADER, GLOBAL_HEADER]
+    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER, HEADS_HEADER, TRAIN_HEADER, TARGETS_HEADER, GLOBAL_HEADER, CARAFE_HEADER]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -78,7 +80,8 @@ def header_prototypes(path=HEADER):
 
 
 def _all_prototypes():
-    return header_prototypes() + header_prototypes(HEADS_HEADER) + header_prototypes(TRAIN_HEADER) + header_prototypes(TARGETS_HEADER) + header_prototypes(GLOBAL_HEADER)
+    return (header_prototypes() + header_prototypes(HEADS_HEADER) + header_prototypes(TRAIN_HEADER) + header_prototypes(TARGETS_HEADER) + header_prototypes(GLOBAL_HEADER)
+            + header_prototypes(CARAFE_HEADER))
 
 
 _CTYPES = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64}
@@ -96,7 +99,7 @@ def _ctype(name, ctype):
 
 def _prototype(fn):
     """(restype, [argtypes], (argument names without the trailing stream), (names of the per-call pointer tables `T *const *`),
-    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h, include/monorun_heads.h, include/monorun_train.h, include/monorun_targets.h or include/monorun_global.h declares it.  The headers
+    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h, include/monorun_heads.h, include/monorun_train.h, include/monorun_targets.h, include/monorun_global.h or include/monorun_carafe.h declares it.  The headers
     are read once."""
     global _prototypes
     if _prototypes is None:
@@ -145,7 +148,7 @@ def ptr(t):
 
 def load():
     """Return the ctypes handle; raises if the library has not been built.  restype / argtypes of every `mr_*` entry point come
-    from its prototype in include/monorun_pnp.h, include/monorun_heads.h, include/monorun_train.h, include/monorun_targets.h or include/monorun_global.h (``_prototype``)."""
+    from its prototype in include/monorun_pnp.h, include/monorun_heads.h, include/monorun_train.h, include/monorun_targets.h, include/monorun_global.h or include/monorun_carafe.h (``_prototype``)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -196,3 +199,5 @@ TRAIN_EXPORTED_SYMBOLS = ('mr_noc_decode_train', 'mr_noc_decode_train_backward')
 TARGETS_EXPORTED_SYMBOLS = ('mr_noc_dense_target', 'mr_smooth_l1_mod_workspace_bytes', 'mr_smooth_l1_mod_loss', 'mr_smooth_l1_mod_loss_backward')
 # the entry points of include/monorun_global.h (the global head's Monte-Carlo forward): the same library again
 GLOBAL_EXPORTED_SYMBOLS = ('mr_global_head_mc_workspace_bytes', 'mr_global_head_mc_forward')
+# the entry points of include/monorun_carafe.h (the NOC head trunk's CARAFE upsampler): the same library again
+CARAFE_EXPORTED_SYMBOLS = ('mr_carafe_pack_forward', 'mr_carafe_backward_workspace_bytes', 'mr_carafe_pack_backward')
