@@ -1,7 +1,4 @@
-"""ctypes loader / builder for libmonorun_pnp.so (the C ABI declared in include/monorun_pnp.h and, for the head kernels behind the
-PnP, include/monorun_heads.h, for the training decode, include/monorun_train.h, and for the NOC targets and loss_noc,
-include/monorun_targets.h, for the global head, include/monorun_global.h, and for the NOC head trunk's CARAFE upsampler,
-include/monorun_carafe.h).
+"""ctypes loader / builder for libmonorun_pnp.so: the C ABI that the headers of ``HEADERS`` declare (include/*.h, one per subsystem).
 
 The library is built in-tree by hipcc for gfx950 (``build()``; also driven by
 ``__graft_entry__.build()``) and loaded with ctypes — cffi, which the reference uses
@@ -18,13 +15,41 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 SRC = os.path.join(_HERE, 'csrc', 'monorun_pnp.hip')
 INCLUDE = os.path.join(_ROOT, 'include')
-HEADER = os.path.join(INCLUDE, 'monorun_pnp.h')
-HEADS_HEADER = os.path.join(INCLUDE, 'monorun_heads.h')      # the head kernels' entry points: same library, a header of their own
-TRAIN_HEADER = os.path.join(INCLUDE, 'monorun_train.h')      # the training decode's entry points: likewise
-TARGETS_HEADER = os.path.join(INCLUDE, 'monorun_targets.h')  # the dense NOC targets' and loss_noc's entry points: likewise
-GLOBAL_HEADER = os.path.join(INCLUDE, 'monorun_global.h')    # the global head's entry points: likewise
-CARAFE_HEADER = os.path.join(INCLUDE, 'monorun_carafe.h')    # the CARAFE upsampler's entry points: likewise
 SO = os.environ.get('MR_PNP_SO') or os.path.join(_HERE, 'libmonorun_pnp.so')     # MR_PNP_SO: A/B-test another build of the library
+
+# The public surface of the one library: key -> (header under include/, the entry points it declares in declaration order).  The tuples are
+# written by hand: they pin the surface, so that a change to a header shows up as a change here (tests/test_capi_and_host.py).  A new
+# subsystem adds one row, and `_stale`, `load` and the prototypes follow.  `pnp` is the cffi surface of INTEGRATION.md section 3 (with the
+# reference's three host-buffer symbols of ext.h); the other headers are outside it.
+HEADERS = {
+    'pnp': ('monorun_pnp.h', (
+        'mr_pnp_version', 'mr_pnp_error_string', 'mr_pnp_last_hip_error', 'mr_pnp_device_count', 'mr_pick_waves', 'mr_spin',
+        'mr_pnp_uncert_batched', 'mr_epnp_ransac_batched', 'mr_epnp_workspace_bytes', 'mr_epnp_ransac_grouped', 'mr_pnp_uncert_from_init_batched',
+        'mr_pnp_uncert_from_init_grouped', 'mr_pnp_uncert_from_epnp_grouped', 'mr_cov_symeig_rule', 'mr_pnp6_refine_batched',
+        'mr_pnp_exact_hessian_batched', 'mr_pnp_uncert_backward_batched', 'pnp_uncert',
+        'mr_noc_decode_batched', 'mr_pnp_from_head_batched', 'mr_roi_align_avg', 'mr_nms_bev_batched',
+        'mr_bbox3d_overlaps_aligned', 'mr_uncert_projection', 'mr_uncert_projection_backward', 'mr_robust_kl_workspace_bytes', 'mr_robust_kl_loss',
+        'mr_robust_kl_loss_backward',
+        'mr_kitti_overlaps', 'mr_kitti_match_workspace_bytes', 'mr_kitti_match',
+        'pnp_noc_uncert', 'pnp_noc_cov_uncert', 'mr_pnp_noc_batched')),
+    'heads': ('monorun_heads.h', ('mr_score_head_forward',)),
+    'train': ('monorun_train.h', ('mr_noc_decode_train', 'mr_noc_decode_train_backward')),                             # section 14
+    'targets': ('monorun_targets.h', ('mr_noc_dense_target', 'mr_smooth_l1_mod_workspace_bytes', 'mr_smooth_l1_mod_loss',
+                                      'mr_smooth_l1_mod_loss_backward')),                                               # section 15
+    'global': ('monorun_global.h', ('mr_global_head_mc_workspace_bytes', 'mr_global_head_mc_forward')),                # section 16
+    'carafe': ('monorun_carafe.h', ('mr_carafe_pack_forward', 'mr_carafe_backward_workspace_bytes', 'mr_carafe_pack_backward')),   # section 17
+}
+
+
+def header_path(key):
+    """The file of one of the headers of ``HEADERS``."""
+    return os.path.join(INCLUDE, HEADERS[key][0])
+
+
+def exported_symbols(key=None):
+    """The pinned entry points of one header, or of all of them in table order."""
+    return HEADERS[key][1] if key is not None else tuple(n for _, names in HEADERS.values() for n in names)
+
 
 MR_F32, MR_F16, MR_F64, MR_BF16 = 0, 1, 2, 3
 MR_MEAN_AUTO, MR_MEAN_SEQUENTIAL, MR_MEAN_PAIRWISE, MR_MEAN_MASK = 0, 1, 2, 3          # MR_MEAN_MASK: the two bits of the istd mean's order
@@ -48,7 +73,7 @@ def _stale():
         return True
     t = os.path.getmtime(SO)
     csrc = os.path.join(_HERE, 'csrc')
-    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [HEADER, HEADS_HEADER, TRAIN_HEADER, TARGETS_HEADER, GLOBAL_HEADER, CARAFE_HEADER]
+    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [header_path(k) for k in HEADERS]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -65,9 +90,9 @@ def build(force=False, verbose=False):
     return SO
 
 
-def header_prototypes(path=HEADER):
-    """[(name, 'return type', ['arg type name', ...])] for every function the header declares."""
-    src = open(path).read()
+def header_prototypes(path=None):
+    """[(name, 'return type', ['arg type name', ...])] for every function the header declares (default: the `pnp` header, the cffi surface)."""
+    src = open(path or header_path('pnp')).read()
     src = re.sub(r'/\*.*?\*/', ' ', src, flags=re.S)
     src = re.sub(r'//[^\n]*', ' ', src)
     src = '\n'.join(l for l in src.split('\n') if not l.lstrip().startswith('#') and 'extern "C"' not in l and l.strip() != '}')
@@ -80,8 +105,7 @@ def header_prototypes(path=HEADER):
 
 
 def _all_prototypes():
-    return (header_prototypes() + header_prototypes(HEADS_HEADER) + header_prototypes(TRAIN_HEADER) + header_prototypes(TARGETS_HEADER) + header_prototypes(GLOBAL_HEADER)
-            + header_prototypes(CARAFE_HEADER))
+    return [p for k in HEADERS for p in header_prototypes(header_path(k))]
 
 
 _CTYPES = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64}
@@ -99,8 +123,7 @@ def _ctype(name, ctype):
 
 def _prototype(fn):
     """(restype, [argtypes], (argument names without the trailing stream), (names of the per-call pointer tables `T *const *`),
-    frozenset of the names) of an `mr_*` entry point, as include/monorun_pnp.h, include/monorun_heads.h, include/monorun_train.h, include/monorun_targets.h, include/monorun_global.h or include/monorun_carafe.h declares it.  The headers
-    are read once."""
+    frozenset of the names) of an `mr_*` entry point, as its header of ``HEADERS`` declares it.  The headers are read once."""
     global _prototypes
     if _prototypes is None:
         protos = {}
@@ -148,7 +171,7 @@ def ptr(t):
 
 def load():
     """Return the ctypes handle; raises if the library has not been built.  restype / argtypes of every `mr_*` entry point come
-    from its prototype in include/monorun_pnp.h, include/monorun_heads.h, include/monorun_train.h, include/monorun_targets.h, include/monorun_global.h or include/monorun_carafe.h (``_prototype``)."""
+    from its prototype in its header of ``HEADERS`` (``_prototype``)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -164,7 +187,7 @@ def load():
             f.restype, argtypes = _prototype(name)[:2]
             if argtypes:
                 f.argtypes = argtypes
-    # development aids for the tests (not in the public header, not in EXPORTED_SYMBOLS)
+    # development aids for the tests (in no public header, not in HEADERS)
     lib.mr_debug_launch_waves.restype = i32
     lib.mr_debug_launch_waves.argtypes = [i32, i32, i32, i32, i32]
     lib.mr_debug_block_sum.restype = i32
@@ -188,16 +211,7 @@ def check(code):
                            f'(code {code}, hip error {lib.mr_pnp_last_hip_error()})')
 
 
-EXPORTED_SYMBOLS = ('mr_pnp_version', 'mr_spin', 'mr_pick_waves', 'mr_pnp_error_string', 'mr_pnp_last_hip_error', 'mr_pnp_device_count',
-                    'mr_pnp_uncert_batched', 'mr_epnp_ransac_batched', 'mr_epnp_ransac_grouped', 'mr_epnp_workspace_bytes', 'mr_pnp_uncert_from_init_batched', 'mr_pnp_uncert_from_init_grouped', 'mr_pnp_uncert_from_epnp_grouped', 'mr_cov_symeig_rule', 'mr_pnp6_refine_batched', 'mr_pnp_exact_hessian_batched', 'mr_pnp_uncert_backward_batched', 'pnp_uncert', 'mr_noc_decode_batched', 'mr_pnp_from_head_batched', 'mr_nms_bev_batched', 'mr_bbox3d_overlaps_aligned', 'mr_uncert_projection', 'mr_uncert_projection_backward', 'mr_robust_kl_workspace_bytes', 'mr_robust_kl_loss', 'mr_robust_kl_loss_backward', 'pnp_noc_uncert', 'pnp_noc_cov_uncert', 'mr_pnp_noc_batched',
-                    'mr_kitti_overlaps', 'mr_kitti_match_workspace_bytes', 'mr_kitti_match', 'mr_roi_align_avg')
-# the entry points of include/monorun_heads.h: the same library, outside the cffi surface of monorun_pnp.h
-HEADS_EXPORTED_SYMBOLS = ('mr_score_head_forward',)
-# the entry points of include/monorun_train.h (the NOC head's training decode): the same library again
-TRAIN_EXPORTED_SYMBOLS = ('mr_noc_decode_train', 'mr_noc_decode_train_backward')
-# the entry points of include/monorun_targets.h (the dense NOC targets and loss_noc): the same library again
-TARGETS_EXPORTED_SYMBOLS = ('mr_noc_dense_target', 'mr_smooth_l1_mod_workspace_bytes', 'mr_smooth_l1_mod_loss', 'mr_smooth_l1_mod_loss_backward')
-# the entry points of include/monorun_global.h (the global head's Monte-Carlo forward): the same library again
-GLOBAL_EXPORTED_SYMBOLS = ('mr_global_head_mc_workspace_bytes', 'mr_global_head_mc_forward')
-# the entry points of include/monorun_carafe.h (the NOC head trunk's CARAFE upsampler): the same library again
-CARAFE_EXPORTED_SYMBOLS = ('mr_carafe_pack_forward', 'mr_carafe_backward_workspace_bytes', 'mr_carafe_pack_backward')
+def call(fn, common={}, /, *, stream, **named):
+    """Launch the entry point `fn` on `stream` (the raw hipStream_t handle) with its arguments given by the header's names (``pack``), and
+    raise unless it returns MR_OK."""
+    check(getattr(load(), fn)(*pack(fn, common, **named), stream))

@@ -95,9 +95,8 @@ class _CarafePackFunction(torch.autograd.Function):
         N, C, H, W = x.shape
         out = torch.empty(N, C, H * s, W * s, device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().mr_carafe_pack_forward(*_lib.pack(
-                'mr_carafe_pack_forward', _sizes(x, k, G, s), x=x.data_ptr(), m=m.data_ptr(), out=out.data_ptr()),
-                torch.cuda.current_stream(x.device).cuda_stream))
+            _lib.call('mr_carafe_pack_forward', _sizes(x, k, G, s), x=x.data_ptr(), m=m.data_ptr(), out=out.data_ptr(),
+                      stream=torch.cuda.current_stream(x.device).cuda_stream)
         ctx.save_for_backward(x, m)
         ctx.cfg = (k, G, s)
         return out
@@ -121,9 +120,9 @@ class _CarafePackFunction(torch.autograd.Function):
         nbytes = lib.mr_carafe_backward_workspace_bytes(*_lib.pack('mr_carafe_backward_workspace_bytes', sizes)) if need_x else 0
         work = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if need_x else None
         with torch.cuda.device(x.device):
-            _lib.check(lib.mr_carafe_pack_backward(*_lib.pack(
-                'mr_carafe_pack_backward', sizes, x=x.data_ptr(), m=m.data_ptr(), grad_out=go.data_ptr(), workspace=_lib.ptr(work),
-                workspace_bytes=nbytes, grad_x=_lib.ptr(grad_x), grad_m=_lib.ptr(grad_m)), torch.cuda.current_stream(x.device).cuda_stream))
+            _lib.call('mr_carafe_pack_backward', sizes, x=x.data_ptr(), m=m.data_ptr(), grad_out=go.data_ptr(), workspace=_lib.ptr(work),
+                      workspace_bytes=nbytes, grad_x=_lib.ptr(grad_x), grad_m=_lib.ptr(grad_m),
+                      stream=torch.cuda.current_stream(x.device).cuda_stream)
         return grad_x, grad_m, None, None, None
 
 

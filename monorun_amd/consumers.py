@@ -35,7 +35,7 @@ def xywhr2xyxyr(boxes_xywhr):
 def nms_bev(boxes_xyxyr_list, scores_list, thr):
     """Batched rotated-BEV NMS: one group per list entry, ONE launch.  Returns a list of int64 tensors of
     kept indices (local to each group, descending score)."""
-    lib = _lib.load()
+    _lib.load()
     dev = boxes_xyxyr_list[0].device
     if dev.type != 'cuda':
         raise RuntimeError('monorun_amd.consumers.nms_bev runs on an MI355X only (no CPU fallback)')
@@ -48,8 +48,9 @@ def nms_bev(boxes_xyxyr_list, scores_list, thr):
     keep = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
     num = torch.zeros(groups, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.mr_nms_bev_batched(boxes.data_ptr(), scores.data_ptr(), offsets.data_ptr(), groups, max(sizes) if sizes else 0,
-                                          float(thr), keep.data_ptr(), num.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        _lib.call('mr_nms_bev_batched', boxes_xyxyr=boxes.data_ptr(), scores=scores.data_ptr(), offsets=offsets.data_ptr(), groups=groups,
+                  max_group=max(sizes) if sizes else 0, thr=float(thr), keep=keep.data_ptr(), num_keep=num.data_ptr(),
+                  stream=torch.cuda.current_stream(dev).cuda_stream)
     num_h = num.cpu().tolist()
     off_h = offsets.cpu().tolist()
     return [keep[off_h[g]:off_h[g] + num_h[g]] for g in range(groups)]

@@ -118,8 +118,9 @@ class _Session:
         else:
             arith32, out32 = int(self.dt.box3d_dtype == np.float32 and self.gt.box3d_dtype == np.float32), 1
         st = torch.cuda.current_stream().cuda_stream
-        _lib.check(self.lib.mr_kitti_overlaps(metric, arith32, out32, self.n_img, self.d_dt_off.data_ptr(), self.d_gt_off.data_ptr(),
-                                              d_off.data_ptr(), total, self.d_dt_rows.data_ptr(), self.d_gt_rows.data_ptr(), ov.data_ptr(), st))
+        _lib.call('mr_kitti_overlaps', metric=metric, arith32=arith32, out32=out32, n_img=self.n_img, dt_off=self.d_dt_off.data_ptr(),
+                  gt_off=self.d_gt_off.data_ptr(), ov_off=d_off.data_ptr(), total_pairs=total, dt_box=self.d_dt_rows.data_ptr(),
+                  gt_box=self.d_gt_rows.data_ptr(), overlaps=ov.data_ptr(), stream=st)
         self._ov[metric] = (ov, d_off, ov_off)
         return self._ov[metric]
 
@@ -200,12 +201,12 @@ def eval_class(gt_annos, dt_annos, current_classes, difficultys, metric, min_ove
     st = torch.cuda.current_stream().cuda_stream
 
     def launch(second, thr, nthr, match, pr, ws, ws_bytes):
-        _lib.check(lib.mr_kitti_match(
-            second, metric, int(bool(compute_aos)), alpha32, dtdata32, s.n_img, s.max_det,
-            s.d_dt_off.data_ptr(), s.d_gt_off.data_ptr(), d_ov_off.data_ptr(), s.d_dc_off.data_ptr(), total_dt, total_gt,
-            ov.data_ptr(), s.d_dt_rows.data_ptr(), s.d_dt_alpha.data_ptr(), s.d_gt_alpha.data_ptr(), s.d_dc_box.data_ptr(),
-            d_ig.data_ptr(), d_idt.data_ptr(), nc, d_cd.data_ptr(), d_mo.data_ptr(),
-            thr, nthr, match, pr, ws, ws_bytes, st))
+        _lib.call('mr_kitti_match', second_pass=second, metric=metric, compute_aos=int(bool(compute_aos)), alpha32=alpha32, dtdata32=dtdata32,
+                  n_img=s.n_img, max_det=s.max_det, dt_off=s.d_dt_off.data_ptr(), gt_off=s.d_gt_off.data_ptr(), ov_off=d_ov_off.data_ptr(),
+                  dc_off=s.d_dc_off.data_ptr(), total_dt=total_dt, total_gt=total_gt, overlaps=ov.data_ptr(), dt_box=s.d_dt_rows.data_ptr(),
+                  dt_alpha=s.d_dt_alpha.data_ptr(), gt_alpha=s.d_gt_alpha.data_ptr(), dc_box=s.d_dc_box.data_ptr(), ign_gt=d_ig.data_ptr(),
+                  ign_dt=d_idt.data_ptr(), n_combo=nc, combo_cd=d_cd.data_ptr(), combo_min_overlap=d_mo.data_ptr(), thresholds=thr, n_thr=nthr,
+                  match_score=match, pr=pr, workspace=ws, workspace_bytes=ws_bytes, stream=st)
 
     # pass 1: the scores of the true positives at threshold 0 (eval.py:499-516)
     match = torch.full((nc, max(total_gt, 1)), float('nan'), dtype=torch.float64, device=dev)

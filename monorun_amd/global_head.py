@@ -308,11 +308,10 @@ class FCExtractorMonteCarlo(FCExtractor):
         if work.dtype != torch.float32 or work.device != dev or not work.is_contiguous() or work.numel() * 4 < nbytes:
             raise ValueError(f'mc_forward_hip: the workspace must be a contiguous fp32 tensor of at least {nbytes // 4} elements on {dev}')
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_global_head_mc_forward(*_lib.pack(
-                'mr_global_head_mc_forward', sizes, x=x.detach().data_ptr(), w1=w[0].data_ptr(), b1=w[1].data_ptr(), w2=w[2].data_ptr(),
-                b2=w[3].data_ptr(), w_reg=w[4].data_ptr(), b_reg=w[5].data_ptr(), keep0=keep[0].data_ptr(), keep1=keep[1].data_ptr(),
-                keep2=keep[2].data_ptr(), q0=1.0 / (1.0 - self.dropout2d_rate), q1=1.0 / (1.0 - self.dropout_rate),
-                workspace=work.data_ptr(), workspace_bytes=nbytes, mean=mean.data_ptr(), var=var.data_ptr(), reg_fc_out=reg.data_ptr(),
-                samples=_lib.ptr(samples)), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_global_head_mc_forward', sizes, x=x.detach().data_ptr(), w1=w[0].data_ptr(), b1=w[1].data_ptr(), w2=w[2].data_ptr(),
+                      b2=w[3].data_ptr(), w_reg=w[4].data_ptr(), b_reg=w[5].data_ptr(), keep0=keep[0].data_ptr(), keep1=keep[1].data_ptr(),
+                      keep2=keep[2].data_ptr(), q0=1.0 / (1.0 - self.dropout2d_rate), q1=1.0 / (1.0 - self.dropout_rate), workspace=work.data_ptr(),
+                      workspace_bytes=nbytes, mean=mean.data_ptr(), var=var.data_ptr(), reg_fc_out=reg.data_ptr(), samples=_lib.ptr(samples),
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
         out = (mean, var, None, None, reg)
         return out + (samples,) if return_samples else out

@@ -58,11 +58,10 @@ def bbox3d_overlaps_aligned(boxes, qboxes, criterion=-1, z_axis=1, z_center=1.0,
         iou = torch.empty(n, 1, device=dev, dtype=torch.float32)
         rinc = torch.empty(n, device=dev, dtype=torch.float32) if return_rinc else None
         if n:
-            lib = _lib.load()
             with torch.cuda.device(dev):
-                _lib.check(lib.mr_bbox3d_overlaps_aligned(b.data_ptr(), bs, q.data_ptr(), qs, n, int(criterion), int(z_axis), float(z_center),
-                                                          HEIGHT_RULES[height_rule], iou.data_ptr(), rinc.data_ptr() if rinc is not None else None,
-                                                          torch.cuda.current_stream(dev).cuda_stream))
+                _lib.call('mr_bbox3d_overlaps_aligned', boxes=b.data_ptr(), boxes_row_stride=bs, qboxes=q.data_ptr(), qboxes_row_stride=qs, n=n,
+                          criterion=int(criterion), z_axis=int(z_axis), z_center=float(z_center), flags=HEIGHT_RULES[height_rule],
+                          iou=iou.data_ptr(), rinc=_lib.ptr(rinc), stream=torch.cuda.current_stream(dev).cuda_stream)
     if src != dev:
         iou = iou.to(src)
         rinc = rinc.to(src) if rinc is not None else None

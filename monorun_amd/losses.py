@@ -120,9 +120,10 @@ class _RobustKLFunction(torch.autograd.Function):
         c = torch.empty((), device=dev, dtype=torch.float32)
         ws = torch.empty(int(lib.mr_robust_kl_workspace_bytes(numel)), device=dev, dtype=torch.uint8)
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_robust_kl_loss(pred.data_ptr(), logstd.data_ptr(), numel, mode, delta, eps, momentum, int(training),
-                                             reduction, loss_weight, buf.data_ptr(), loss.data_ptr(), c.data_ptr(), ws.data_ptr(),
-                                             ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_robust_kl_loss', pred=pred.data_ptr(), logstd=logstd.data_ptr(), numel=numel, target_mode=mode, delta=delta, eps=eps,
+                      momentum=momentum, training=int(training), reduction=reduction, loss_weight=loss_weight, mean_inv_std=buf.data_ptr(),
+                      loss=loss.data_ptr(), c_out=c.data_ptr(), workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
         ctx.save_for_backward(pred, logstd, c)
         ctx.args = (mode, delta, eps, reduction, loss_weight)
         return loss
@@ -136,9 +137,9 @@ class _RobustKLFunction(torch.autograd.Function):
         gp, gl = torch.empty_like(pred), torch.empty_like(logstd)
         dev = pred.device
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().mr_robust_kl_loss_backward(pred.data_ptr(), logstd.data_ptr(), pred.numel(), mode, delta, eps, reduction,
-                                                              loss_weight, grad.data_ptr(), c.data_ptr(), gp.data_ptr(), gl.data_ptr(),
-                                                              torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_robust_kl_loss_backward', pred=pred.data_ptr(), logstd=logstd.data_ptr(), numel=pred.numel(), target_mode=mode,
+                      delta=delta, eps=eps, reduction=reduction, loss_weight=loss_weight, grad_loss=grad.data_ptr(), c=c.data_ptr(),
+                      grad_pred=gp.data_ptr(), grad_logstd=gl.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
         return gp, gl, None, None, None, None, None, None, None, None
 
 
@@ -227,8 +228,8 @@ class _SmoothL1ModFunction(torch.autograd.Function):
         ctx.common = dict(pred=pred.data_ptr(), target=target.data_ptr(), weight=_lib.ptr(weight), weight_mode=weight_mode, numel=numel,
                           channels=channels, hw=hw, beta=beta, reduction=reduction, loss_weight=loss_weight)
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_smooth_l1_mod_loss(*_lib.pack('mr_smooth_l1_mod_loss', ctx.common, loss=loss.data_ptr(), workspace=ws.data_ptr(),
-                                                            workspace_bytes=ws.numel()), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_smooth_l1_mod_loss', ctx.common, loss=loss.data_ptr(), workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
         ctx.save_for_backward(pred, target, weight)
         ctx.args = (beta, reduction, loss_weight)
         return loss
@@ -248,8 +249,8 @@ class _SmoothL1ModFunction(torch.autograd.Function):
         gp = torch.empty_like(pred)
         dev = pred.device
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().mr_smooth_l1_mod_loss_backward(*_lib.pack('mr_smooth_l1_mod_loss_backward', ctx.common, grad_loss=grad.data_ptr(),
-                                                                             grad_pred=gp.data_ptr()), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_smooth_l1_mod_loss_backward', ctx.common, grad_loss=grad.data_ptr(), grad_pred=gp.data_ptr(),
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
         return (gp,) + (None,) * 8
 
 

@@ -87,9 +87,8 @@ class _DecodeFunction(torch.autograd.Function):
                    proj_logstd_px=maps2[1], dims=dims, dims_var=dims_var)
         ctx.common = _common_args(all_pred, labels, flip, dim, dim_var, consts, scalars)
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().mr_noc_decode_train(*_lib.pack(
-                'mr_noc_decode_train', ctx.common, distances=_lib.ptr(distances), distance_min=scalars['distance_min'],
-                **{k: _lib.ptr(v) for k, v in out.items()}), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_noc_decode_train', ctx.common, distances=_lib.ptr(distances), distance_min=scalars['distance_min'],
+                      **{k: _lib.ptr(v) for k, v in out.items()}, stream=torch.cuda.current_stream(dev).cuda_stream)
         ctx.save_for_backward(all_pred, dim, dim_var, labels, flip, distances, *consts)
         ctx.scalars = scalars
         ctx.set_materialize_grads(False)
@@ -107,10 +106,9 @@ class _DecodeFunction(torch.autograd.Function):
         grad_dim = torch.empty_like(dim)
         grad_dim_var = torch.empty_like(dim_var) if dim_var is not None else None
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().mr_noc_decode_train_backward(*_lib.pack(
-                'mr_noc_decode_train_backward', ctx.common, grad_all_pred=grad_all_pred.data_ptr(), grad_dim=grad_dim.data_ptr(),
-                grad_dim_var=_lib.ptr(grad_dim_var), **{'grad_' + k: _lib.ptr(g) for k, g in zip(OUTPUTS, grads)}),
-                torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_noc_decode_train_backward', ctx.common, grad_all_pred=grad_all_pred.data_ptr(), grad_dim=grad_dim.data_ptr(),
+                      grad_dim_var=_lib.ptr(grad_dim_var), **{'grad_' + k: _lib.ptr(g) for k, g in zip(OUTPUTS, grads)},
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
         return grad_all_pred, grad_dim, grad_dim_var, None, None, None, None, None
 
 

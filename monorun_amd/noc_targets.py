@@ -240,8 +240,7 @@ def _noc_targets_hip(pos_bboxes_list, pos_assigned_gt_inds_list, gt_coords_3d, g
     assert all(t.is_contiguous() and t.device == dev for t in out) and targets.dtype == weights.dtype == torch.float32
     mu, sd = _const(means, dev), _const(stds, dev)
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().mr_noc_dense_target(*_lib.pack(
-            'mr_noc_dense_target', tables, num_images=L, rois=rois.data_ptr(), roi_img=roi_img.data_ptr(), roi_gt=roi_gt.data_ptr(), n=n, h=h, w=w,
-            target_means=mu.data_ptr(), target_stds=sd.data_ptr(), eps_coder=float(eps_c), eps_target=float(eps),
-            targets=targets.data_ptr(), weights=weights.data_ptr(), counts=cnt.data_ptr()), torch.cuda.current_stream(dev).cuda_stream))
+        _lib.call('mr_noc_dense_target', tables, num_images=L, rois=rois.data_ptr(), roi_img=roi_img.data_ptr(), roi_gt=roi_gt.data_ptr(), n=n, h=h,
+                  w=w, target_means=mu.data_ptr(), target_stds=sd.data_ptr(), eps_coder=float(eps_c), eps_target=float(eps),
+                  targets=targets.data_ptr(), weights=weights.data_ptr(), counts=cnt.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
     return targets, weights, cnt

@@ -103,10 +103,9 @@ def pnp_uncert_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, v
     outs, out_args = _outputs(dev, B, P, with_diag)
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp_uncert_batched(*_lib.pack(
-                'mr_pnp_uncert_batched', common, ransac_thr=_lib.ptr(keep['ransac_thr']), init_pose=_lib.ptr(keep['init_pose']), B=B, P=P, z_min=float(z_min),
-                istd_thres=float(epnp_istd_thres), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags), **out_args),
-                torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_pnp_uncert_batched', common, ransac_thr=_lib.ptr(keep['ransac_thr']), init_pose=_lib.ptr(keep['init_pose']), B=B, P=P,
+                      z_min=float(z_min), istd_thres=float(epnp_istd_thres), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags),
+                      **out_args, stream=torch.cuda.current_stream(dev).cuda_stream)
     return outs
 
 
@@ -126,11 +125,10 @@ def epnp_ransac_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, epnp_istd
             # the launches of the call hand their intermediate results over in a workspace: from torch's caching allocator, on the
             # stream the launches go to (the block returns to the allocator when `work` dies; stream order keeps that safe)
             work = torch.empty(int(lib.mr_epnp_workspace_bytes(B, P)), device=dev, dtype=torch.uint8)
-            _lib.check(lib.mr_epnp_ransac_batched(*_lib.pack(
-                'mr_epnp_ransac_batched', common, ransac_thr=_lib.ptr(keep['ransac_thr']), B=B, P=P, istd_thres=float(epnp_istd_thres),
-                flags=_first_round_flags(flags, first_round), max_iters=int(max_iters), init_pose=init_pose.data_ptr(), init_mask=init_mask.data_ptr(),
-                init_valid=init_valid.data_ptr(), diag=_lib.ptr(diag), debug_hypotheses=_lib.ptr(hyp), workspace=work.data_ptr(), workspace_bytes=work.numel()),
-                torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_epnp_ransac_batched', common, ransac_thr=_lib.ptr(keep['ransac_thr']), B=B, P=P, istd_thres=float(epnp_istd_thres),
+                      flags=_first_round_flags(flags, first_round), max_iters=int(max_iters), init_pose=init_pose.data_ptr(),
+                      init_mask=init_mask.data_ptr(), init_valid=init_valid.data_ptr(), diag=_lib.ptr(diag), debug_hypotheses=_lib.ptr(hyp),
+                      workspace=work.data_ptr(), workspace_bytes=work.numel(), stream=torch.cuda.current_stream(dev).cuda_stream)
     return init_pose, init_mask, init_valid, diag, hyp
 
 
@@ -145,10 +143,9 @@ def pnp_uncert_from_init_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, 
     outs, out_args = _outputs(dev, B, P, with_diag)
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp_uncert_from_init_batched(*_lib.pack(
-                'mr_pnp_uncert_from_init_batched', common, init_pose=keep['init_pose'].data_ptr(), init_mask=im.data_ptr(), init_valid=iv.data_ptr(),
-                B=B, P=P, z_min=float(z_min), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags), **out_args),
-                torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_pnp_uncert_from_init_batched', common, init_pose=keep['init_pose'].data_ptr(), init_mask=im.data_ptr(),
+                      init_valid=iv.data_ptr(), B=B, P=P, z_min=float(z_min), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags),
+                      **out_args, stream=torch.cuda.current_stream(dev).cuda_stream)
     return outs
 
 
@@ -172,26 +169,24 @@ def pnp_uncert_epnp_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_ran
             st = torch.cuda.current_stream(dev).cuda_stream
             work = torch.empty(int(lib.mr_epnp_workspace_bytes(B, P)), device=dev, dtype=torch.uint8)     # (stream order keeps its reuse safe)
             work_args = dict(workspace=work.data_ptr(), workspace_bytes=work.numel())
-            _lib.check(lib.mr_epnp_ransac_batched(*_lib.pack(
-                'mr_epnp_ransac_batched', common, ransac_thr=_lib.ptr(keep['ransac_thr']), B=B, P=P, istd_thres=float(epnp_istd_thres),
-                flags=_first_round_flags(int(flags) & _INIT_FLAGS, first_round) | _lib.MR_EPNP_DEFER_REFIT, max_iters=int(max_iters), **init_args,
-                diag=None, debug_hypotheses=None, **work_args), st))
-            _lib.check(lib.mr_pnp_uncert_from_epnp_grouped(*_lib.pack(
-                fused, common, ncalls=1, **tables, epnp_diag=None, B=B, P=P, z_min=float(z_min), inlier_opt_only=int(bool(inlier_opt_only)),
-                flags=int(flags), cov_calib_logscale=None, cov_corr_sd=0.0, cov_calib=None, **work_args), st))
+            _lib.call('mr_epnp_ransac_batched', common, ransac_thr=_lib.ptr(keep['ransac_thr']), B=B, P=P, istd_thres=float(epnp_istd_thres),
+                      flags=_first_round_flags(int(flags) & _INIT_FLAGS, first_round) | _lib.MR_EPNP_DEFER_REFIT, max_iters=int(max_iters),
+                      **init_args, diag=None, debug_hypotheses=None, **work_args, stream=st)
+            _lib.call(fused, common, ncalls=1, **tables, epnp_diag=None, B=B, P=P, z_min=float(z_min), inlier_opt_only=int(bool(inlier_opt_only)),
+                      flags=int(flags), cov_calib_logscale=None, cov_corr_sd=0.0, cov_calib=None, **work_args, stream=st)
     return outs + (init_pose, init_valid)
 
 
 def cov_symeig_rule_device(valid_u8, cov, with_eigs=False):
     """The reference's eigenvalue rule (pnp_uncert.py:77-85) applied IN PLACE to (valid u8 (B,), cov f32 (B,4,4)):
     objects with lambda_min(h) <= max(1e-6 lambda_max(h), 0) become invalid and get cov = I (``mr_cov_symeig_rule``)."""
-    lib = _lib.load()
     B = int(valid_u8.shape[0])
     assert valid_u8.dtype == torch.uint8 and cov.dtype == torch.float32 and cov.is_contiguous() and valid_u8.is_contiguous()
     lam = torch.empty(B, 2, device=cov.device, dtype=torch.float32) if with_eigs else None
     if B > 0:
         with torch.cuda.device(cov.device):
-            _lib.check(lib.mr_cov_symeig_rule(valid_u8.data_ptr(), cov.data_ptr(), B, _lib.ptr(lam), torch.cuda.current_stream(cov.device).cuda_stream))
+            _lib.call('mr_cov_symeig_rule', valid=valid_u8.data_ptr(), cov=cov.data_ptr(), B=B, eig_min_max=_lib.ptr(lam),
+                      stream=torch.cuda.current_stream(cov.device).cuda_stream)
     return lam
 
 
@@ -440,7 +435,6 @@ class PnPPipeline:
 
     def _pick_streams(self, want, avoid):
         import time
-        lib = _lib.load()
         US = 40
 
         def wall(a, b):
@@ -448,8 +442,8 @@ class PnPPipeline:
             for _ in range(3):
                 a.synchronize(); b.synchronize()
                 t0 = time.perf_counter()
-                _lib.check(lib.mr_spin(US, a.cuda_stream))
-                _lib.check(lib.mr_spin(US, b.cuda_stream))
+                _lib.call('mr_spin', microseconds=US, stream=a.cuda_stream)
+                _lib.call('mr_spin', microseconds=US, stream=b.cuda_stream)
                 a.synchronize(); b.synchronize()
                 best = min(best, time.perf_counter() - t0)
             return best * 1e6
@@ -524,10 +518,9 @@ def pnp6_refine_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range, 
     diag = torch.empty(B, 2, **f32) if with_diag else None
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp6_refine_batched(*_lib.pack(
-                'mr_pnp6_refine_batched', common, inlier_mask=mask.data_ptr(), pose4=pose4.data_ptr(), valid4=valid4.data_ptr(), B=B, P=P,
-                z_min=float(z_min), flags=int(flags), valid=valid.data_ptr(), pose6=pose6.data_ptr(), cov6=cov6.data_ptr(), diag=_lib.ptr(diag)),
-                torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_pnp6_refine_batched', common, inlier_mask=mask.data_ptr(), pose4=pose4.data_ptr(), valid4=valid4.data_ptr(), B=B, P=P,
+                      z_min=float(z_min), flags=int(flags), valid=valid.data_ptr(), pose6=pose6.data_ptr(), cov6=cov6.data_ptr(),
+                      diag=_lib.ptr(diag), stream=torch.cuda.current_stream(dev).cuda_stream)
     return valid, pose6, cov6, diag
 
 
@@ -546,9 +539,8 @@ def exact_hessian_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u_range
     hess = torch.empty(B, 4, 4, **f32) if with_hessian else None
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp_exact_hessian_batched(*_lib.pack(
-                'mr_pnp_exact_hessian_batched', common, pose=pose.data_ptr(), inlier_mask=_lib.ptr(mask), B=B, P=P, z_min=float(z_min),
-                valid=valid.data_ptr(), hess=_lib.ptr(hess), cov=cov.data_ptr()), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_pnp_exact_hessian_batched', common, pose=pose.data_ptr(), inlier_mask=_lib.ptr(mask), B=B, P=P, z_min=float(z_min),
+                      valid=valid.data_ptr(), hess=_lib.ptr(hess), cov=cov.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
     return valid, cov, hess
 
 
@@ -579,10 +571,10 @@ def pnp_uncert_backward_device(coords_2d, coords_2d_istd, coords_3d, cam_mats, u
     status = torch.empty(B, device=dev, dtype=torch.uint8) if with_status else None
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp_uncert_backward_batched(*_lib.pack(
-                'mr_pnp_uncert_backward_batched', common, pose=pose.data_ptr(), inlier_mask=_lib.ptr(mask), valid=valid.data_ptr(),
-                lm_all_points=int(bool(lm_all_points)), grad_pose=_lib.ptr(gp), cov=_lib.ptr(c), grad_cov=_lib.ptr(gc), B=B, P=P, z_min=float(z_min),
-                grad_x2d=_lib.ptr(g2), grad_istd=_lib.ptr(gw), grad_x3d=_lib.ptr(g3), status=_lib.ptr(status)), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_pnp_uncert_backward_batched', common, pose=pose.data_ptr(), inlier_mask=_lib.ptr(mask), valid=valid.data_ptr(),
+                      lm_all_points=int(bool(lm_all_points)), grad_pose=_lib.ptr(gp), cov=_lib.ptr(c), grad_cov=_lib.ptr(gc), B=B, P=P,
+                      z_min=float(z_min), grad_x2d=_lib.ptr(g2), grad_istd=_lib.ptr(gw), grad_x3d=_lib.ptr(g3), status=_lib.ptr(status),
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
     return g2, gw, g3, status
 
 

@@ -168,7 +168,7 @@ def gen_coord_2d(h, w, pad_to=32, flip=False, scale=None, device=None):
 def roi_align_avg(input, rois, output_size, spatial_scale=1.0, sampling_ratio=0, aligned=True):
     """mmcv.ops.roi_align(input, rois, output_size, spatial_scale, sampling_ratio, 'avg', aligned) forward
     (``mr_roi_align_avg``).  input (N,C,H,W) f32 on the GPU, rois (K,5) [batch_idx, x1, y1, x2, y2] -> (K,C,oh,ow)."""
-    lib = _lib.load()
+    _lib.load()
     dev = input.device
     if dev.type != 'cuda':
         raise RuntimeError('monorun_amd.roi_align_avg runs on an MI355X only (no CPU fallback)')
@@ -179,8 +179,9 @@ def roi_align_avg(input, rois, output_size, spatial_scale=1.0, sampling_ratio=0,
     out = torch.empty(r.shape[0], C, oh, ow, device=dev, dtype=torch.float32)
     if r.shape[0]:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_roi_align_avg(x.data_ptr(), r.data_ptr(), r.shape[0], C, H, W, oh, ow, float(spatial_scale), int(sampling_ratio),
-                                            int(bool(aligned)), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_roi_align_avg', input=x.data_ptr(), rois=r.data_ptr(), K=r.shape[0], C=C, H=H, W=W, out_h=oh, out_w=ow,
+                      spatial_scale=float(spatial_scale), sampling_ratio=int(sampling_ratio), aligned=int(bool(aligned)), output=out.data_ptr(),
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
     return out
 
 
@@ -236,11 +237,10 @@ def noc_decode(all_pred, labels, flip, dim, dim_var, rois, num_classes=3, class_
     thr = torch.empty(B, **f32) if epnp_ransac_thres_ratio is not None else None
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_noc_decode_batched(*_lib.pack(
-                'mr_noc_decode_batched', **_decode_args(ap, ap_dt, lab, fl, dm, dv, r, num_classes, class_agnostic, (mu, sd, nm, ns), ref_length, ref_focal_y,
-                                                        target_std, epistemic_std_gain, std_scale, epnp_ransac_thres_ratio),
-                coords_2d=c2d.data_ptr(), coords_2d_istd=istd.data_ptr(), coords_3d=c3d.data_ptr(), dims=dims.data_ptr(), dims_var=_lib.ptr(dims_var),
-                ransac_thr=_lib.ptr(thr), **_coord_map_args(_coord_map(coord_2d, dev))), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_noc_decode_batched', **_decode_args(ap, ap_dt, lab, fl, dm, dv, r, num_classes, class_agnostic, (mu, sd, nm, ns),
+                      ref_length, ref_focal_y, target_std, epistemic_std_gain, std_scale, epnp_ransac_thres_ratio), coords_2d=c2d.data_ptr(),
+                      coords_2d_istd=istd.data_ptr(), coords_3d=c3d.data_ptr(), dims=dims.data_ptr(), dims_var=_lib.ptr(dims_var),
+                      ransac_thr=_lib.ptr(thr), **_coord_map_args(_coord_map(coord_2d, dev)), stream=torch.cuda.current_stream(dev).cuda_stream)
     return dict(coords_2d=c2d, coords_2d_istd=istd, coords_3d=c3d, dims=dims, dims_var=dims_var, ransac_thr=thr)
 
 
@@ -345,14 +345,14 @@ def pnp_from_head(all_pred, labels, flip, dim, dim_var, rois, cam_intrinsic, img
     ls = prep(cov_calib_logscale) if calib else None
     if B > 0:
         with torch.cuda.device(dev):
-            _lib.check(lib.mr_pnp_from_head_batched(*_lib.pack(
-                'mr_pnp_from_head_batched', **_decode_args(ap, ap_dt, lab, fl, dm, dv, r, num_classes, class_agnostic, (mu, sd, nm, ns), ref_length, ref_focal_y,
-                                                           target_std, epistemic_std_gain, std_scale, epnp_ransac_thres_ratio),
-                cam_mats=cam.data_ptr(), cam_batch=cam.shape[0], u_range=ur.data_ptr(), v_range=vr.data_ptr(), range_batch=ur.shape[0],
-                z_min=float(z_min), istd_thres=float(epnp_istd_thres), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags),
-                valid=valid.data_ptr(), pose=pose.data_ptr(), cov=cov.data_ptr(), tr_radius=tr.data_ptr(), inlier_mask=mask.data_ptr(), diag=_lib.ptr(diag),
-                dims=dims.data_ptr(), dims_var=_lib.ptr(dims_var), **_coord_map_args(_coord_map(coord_2d, dev)), cov_calib_logscale=_lib.ptr(ls),
-                cov_corr_sd=float(cov_correction_sd), cov_calib=_lib.ptr(cov_calib)), torch.cuda.current_stream(dev).cuda_stream))
+            _lib.call('mr_pnp_from_head_batched', **_decode_args(ap, ap_dt, lab, fl, dm, dv, r, num_classes, class_agnostic, (mu, sd, nm, ns),
+                      ref_length, ref_focal_y, target_std, epistemic_std_gain, std_scale, epnp_ransac_thres_ratio), cam_mats=cam.data_ptr(),
+                      cam_batch=cam.shape[0], u_range=ur.data_ptr(), v_range=vr.data_ptr(), range_batch=ur.shape[0], z_min=float(z_min),
+                      istd_thres=float(epnp_istd_thres), inlier_opt_only=int(bool(inlier_opt_only)), flags=int(flags), valid=valid.data_ptr(),
+                      pose=pose.data_ptr(), cov=cov.data_ptr(), tr_radius=tr.data_ptr(), inlier_mask=mask.data_ptr(), diag=_lib.ptr(diag),
+                      dims=dims.data_ptr(), dims_var=_lib.ptr(dims_var), **_coord_map_args(_coord_map(coord_2d, dev)),
+                      cov_calib_logscale=_lib.ptr(ls), cov_corr_sd=float(cov_correction_sd), cov_calib=_lib.ptr(cov_calib),
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
     out = (valid.view(torch.bool), pose[:, :1], pose[:, 1:], cov, mask.view(torch.bool), dims, dims_var)
     if with_diag:
         out = out + (diag,)

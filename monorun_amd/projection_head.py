@@ -93,9 +93,9 @@ class _ProjectionFunction(torch.autograd.Function):
         if n:
             dev = coords_3d.device
             with torch.cuda.device(dev):
-                _lib.check(_lib.load().mr_uncert_projection(coords_3d.data_ptr(), pose.data_ptr(), pose.stride(0), cam_intrinsic.data_ptr(),
-                                                            img_shapes.data_ptr(), n, h * w, z_min, allowed_border, out.data_ptr(),
-                                                            torch.cuda.current_stream(dev).cuda_stream))
+                _lib.call('mr_uncert_projection', coords_3d=coords_3d.data_ptr(), pose=pose.data_ptr(), pose_row_stride=pose.stride(0),
+                          cam_intrinsic=cam_intrinsic.data_ptr(), img_shapes=img_shapes.data_ptr(), n=n, hw=h * w, z_min=z_min,
+                          allowed_border=allowed_border, coords_2d=out.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
         ctx.save_for_backward(coords_3d, pose, cam_intrinsic, img_shapes)
         ctx.args = (z_min, allowed_border)
         return out
@@ -111,10 +111,10 @@ class _ProjectionFunction(torch.autograd.Function):
             grad = grad.to(torch.float32).contiguous()
             dev = coords_3d.device
             with torch.cuda.device(dev):
-                _lib.check(_lib.load().mr_uncert_projection_backward(coords_3d.data_ptr(), pose.data_ptr(), pose.stride(0),
-                                                                     cam_intrinsic.data_ptr(), img_shapes.data_ptr(), n, h * w, z_min,
-                                                                     allowed_border, grad.data_ptr(), grad_3d.data_ptr(),
-                                                                     torch.cuda.current_stream(dev).cuda_stream))
+                _lib.call('mr_uncert_projection_backward', coords_3d=coords_3d.data_ptr(), pose=pose.data_ptr(), pose_row_stride=pose.stride(0),
+                          cam_intrinsic=cam_intrinsic.data_ptr(), img_shapes=img_shapes.data_ptr(), n=n, hw=h * w, z_min=z_min,
+                          allowed_border=allowed_border, grad_coords_2d=grad.data_ptr(), grad_coords_3d=grad_3d.data_ptr(),
+                          stream=torch.cuda.current_stream(dev).cuda_stream)
         return grad_3d, None, None, None, None, None
 
 

@@ -289,12 +289,13 @@ def _rows(t, width):
 
 
 def _score_args(head, reg, yaw, t_vec, cov, dims, ret_val_u8, scores_2d, params, out, flags):
+    """The arguments of ``mr_score_head_forward`` by name."""
     n = reg.size(0)
-    return _lib.pack('mr_score_head_forward', reg_fc_out=reg.data_ptr(), reg_fc_out_row_stride=max(reg.stride(0), reg.size(1)),
-                     yaw=yaw.data_ptr(), yaw_row_stride=max(yaw.stride(0), 1), t_vec=t_vec.data_ptr(), t_vec_row_stride=max(t_vec.stride(0), 3),
-                     pose_cov=cov.data_ptr(), dimensions=dims.data_ptr(), dimensions_row_stride=max(dims.stride(0), 3),
-                     ret_val=_lib.ptr(ret_val_u8), scores_2d=_lib.ptr(scores_2d), params=params.data_ptr(), params_numel=params.numel(),
-                     n=n, c1=head.pose_fc_out_channels, c2=head.fc_out_channels, flags=flags, scores=out.data_ptr())
+    return dict(reg_fc_out=reg.data_ptr(), reg_fc_out_row_stride=max(reg.stride(0), reg.size(1)),
+                yaw=yaw.data_ptr(), yaw_row_stride=max(yaw.stride(0), 1), t_vec=t_vec.data_ptr(), t_vec_row_stride=max(t_vec.stride(0), 3),
+                pose_cov=cov.data_ptr(), dimensions=dims.data_ptr(), dimensions_row_stride=max(dims.stride(0), 3),
+                ret_val=_lib.ptr(ret_val_u8), scores_2d=_lib.ptr(scores_2d), params=params.data_ptr(), params_numel=params.numel(),
+                n=n, c1=head.pose_fc_out_channels, c2=head.fc_out_channels, flags=flags, scores=out.data_ptr())
 
 
 def score_head_forward_fused(head, reg_fc_out, yaw, t_vec, pose_cov, dimensions, ret_val=None, scores_2d=None, sigmoid=True):
@@ -304,7 +305,7 @@ def score_head_forward_fused(head, reg_fc_out, yaw, t_vec, pose_cov, dimensions,
     dev = reg_fc_out.device
     if dev.type != 'cuda':
         raise RuntimeError('score_head_forward_fused runs on an MI355X only (no CPU fallback)')
-    lib = _lib.load()
+    _lib.load()
     f32 = dict(device=dev, dtype=torch.float32)
     n = reg_fc_out.size(0)
     reg = _rows(reg_fc_out, head.reg_fc_out_channels)
@@ -315,9 +316,8 @@ def score_head_forward_fused(head, reg_fc_out, yaw, t_vec, pose_cov, dimensions,
     out = torch.empty(n, **f32)
     params = head.packed_params(dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.mr_score_head_forward(*_score_args(head, reg, yaw, t_vec, cov, dims, rv, s2d, params, out,
-                                                          _lib.MR_SCORE_SIGMOID if sigmoid else 0),
-                                             torch.cuda.current_stream(dev).cuda_stream))
+        _lib.call('mr_score_head_forward', _score_args(head, reg, yaw, t_vec, cov, dims, rv, s2d, params, out, _lib.MR_SCORE_SIGMOID if sigmoid else 0),
+                  stream=torch.cuda.current_stream(dev).cuda_stream)
     return out
 
 
@@ -375,8 +375,9 @@ class ScoreHeadLaunch:
         self.out = dict(scores=torch.zeros(n, **f32))
         self.params = score_head.packed_params(device).clone()
         i = self.inputs
-        self.args = _score_args(score_head, i['reg_fc_out'], i['yaw'], i['t_vec'], i['pose_cov'], i['dimensions'], i['ret_val_u8'],
-                                i['det_scores'], self.params, self.out['scores'], _lib.MR_SCORE_SIGMOID if sigmoid else 0)
+        self.args = _lib.pack('mr_score_head_forward', _score_args(
+            score_head, i['reg_fc_out'], i['yaw'], i['t_vec'], i['pose_cov'], i['dimensions'], i['ret_val_u8'], i['det_scores'], self.params,
+            self.out['scores'], _lib.MR_SCORE_SIGMOID if sigmoid else 0))
         self.graph = None
 
     def refresh_params(self):

@@ -1,4 +1,4 @@
-"""The launch shapes the library picks by size, restated as pure functions (csrc/monorun_pnp.hip epnp_ransac_launch,
+"""The launch shapes the library picks by size, restated as pure functions (csrc/pnp_solver_abi.inc epnp_ransac_launch,
 launch_epnp_stages, pick_wpo, widen_for_large_tiles, lm_launch_waves), and the case list of tests/test_gpu_launch_regimes.py.
 The choices change the work, never a result: the GPU tests run every case against the oracle, and check this restatement of the
 wave count against the library's own (mr_debug_launch_waves)."""

@@ -34,7 +34,7 @@ def test_library_loads_and_exports_every_declared_symbol():
     h = _lib.load()
     assert h.mr_pnp_version() == 100
     assert h.mr_pnp_error_string(0) == b'ok' and b'argument' in h.mr_pnp_error_string(-1)
-    for n in _lib.EXPORTED_SYMBOLS:
+    for n in _lib.exported_symbols():
         assert hasattr(h, n)
 
 
@@ -345,32 +345,77 @@ def test_integration_md_cffi_block_is_the_generated_prototype_text_and_every_sym
     from monorun_amd import _lib
     lib = ctypes.CDLL(_lib.SO)
     hdr = {n: len(a) for n, _, a in gen.header_prototypes()}
-    assert set(n for n, _ in protos) == set(hdr) == set(_lib.EXPORTED_SYMBOLS)
+    assert set(n for n, _ in protos) == set(hdr) == set(_lib.exported_symbols('pnp'))
     for name, nargs in protos:
         assert hasattr(lib, name) and hdr[name] == nargs, name
 
 
-def test_loaded_signatures_are_the_header_prototypes():
-    """Every `mr_*` prototype of include/monorun_pnp.h: the loaded function has the declared restype and argtypes of the declared
-    length and types, and no argument name repeats within a prototype (``_lib.pack`` goes by name).  The expected ctypes types are
-    derived here from the header text, not by the loader's own mapping."""
+# what each header of `_lib.HEADERS` declares, pinned a second time here: a change to the public surface shows up in the header, in the
+# loader's table and in this one (`pnp`, the cffi surface: its size, and how many of its symbols are `mr_*`; the names are in INTEGRATION.md)
+_PINNED = {
+    'pnp': 34,
+    'heads': ('mr_score_head_forward',),
+    'train': ('mr_noc_decode_train', 'mr_noc_decode_train_backward'),
+    'targets': ('mr_noc_dense_target', 'mr_smooth_l1_mod_workspace_bytes', 'mr_smooth_l1_mod_loss', 'mr_smooth_l1_mod_loss_backward'),
+    'global': ('mr_global_head_mc_workspace_bytes', 'mr_global_head_mc_forward'),
+    'carafe': ('mr_carafe_pack_forward', 'mr_carafe_backward_workspace_bytes', 'mr_carafe_pack_backward'),
+}
+_SCALAR = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64}
+
+
+def _declared_prototypes(path):
+    """[(return type, name, [arguments])] of a header, by a regex of this file's own (not `_lib.header_prototypes`)."""
+    src = re.sub(r'/\*.*?\*/', ' ', open(path).read(), flags=re.S)
+    found = re.findall(r'^((?:const\s+)?\w+[\s\*]+)(\w+)\s*\(([^)]*)\)\s*;', src, flags=re.M)
+    return [(' '.join(ret.split()), name, [] if args.strip() in ('', 'void') else [' '.join(a.split()) for a in args.split(',')])
+            for ret, name, args in found]
+
+
+@pytest.mark.parametrize('key', ['pnp', 'heads', 'train', 'targets', 'global', 'carafe'])
+def test_loader_binds_every_header(key, monkeypatch):
+    """For each header of `_lib.HEADERS`: the pinned tuple is what the header declares, in order, and shares no name with any other
+    header; the library exports every symbol; the loaded function has the declared restype and argtypes, and `arg_names` the declared
+    names, the expected ones derived here from the header text and not by the loader's own mapping; the header alone makes the
+    library stale."""
     from monorun_amd import _lib
-    lib = _lib.load()
-    src = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(ROOT, 'include', 'monorun_pnp.h')).read(), flags=re.S)
-    scalar = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64}
-    seen = []
-    for ret, name, args in re.findall(r'^((?:const\s+)?\w+[\s\*]+)(mr_\w+)\s*\(([^)]*)\)\s*;', src, flags=re.M):
-        want_ret = ctypes.c_char_p if ret.split() == ['const', 'char', '*'] else scalar[ret.strip()]
-        args = [] if args.strip() in ('', 'void') else [a.strip() for a in args.split(',')]
-        names = [re.search(r'\w+$', a).group() for a in args]
-        want = [ctypes.c_void_p if '*' in a else scalar[a.replace('const ', '').rsplit(None, 1)[0]] for a in args]
+    assert list(_lib.HEADERS) == ['pnp', 'heads', 'train', 'targets', 'global', 'carafe'] and set(_PINNED) == set(_lib.HEADERS)
+    lib, raw = _lib.load(), ctypes.CDLL(_lib.SO)
+    pinned = _lib.exported_symbols(key)
+    assert pinned == _lib.HEADERS[key][1] and _lib.header_path(key) == os.path.join(ROOT, 'include', _lib.HEADERS[key][0])
+    if key == 'pnp':
+        assert len(pinned) == _PINNED[key] and sum(n.startswith('mr_') for n in pinned) == 31
+        assert [n for n, _, _ in _lib.header_prototypes()] == list(pinned)                           # the default header is this one
+    else:
+        assert pinned == _PINNED[key]
+    assert len(set(pinned)) == len(pinned)
+    assert [n for n, _, _ in _lib.header_prototypes(_lib.header_path(key))] == list(pinned)
+    declared = _declared_prototypes(_lib.header_path(key))
+    assert [name for _, name, _ in declared] == list(pinned)
+    for other in _lib.HEADERS:
+        if other != key:
+            assert not set(pinned) & set(_lib.exported_symbols(other)), other
+            assert not set(pinned) & {n for n, _, _ in _lib.header_prototypes(_lib.header_path(other))}, other
+            assert not set(pinned) & {n for _, n, _ in _declared_prototypes(_lib.header_path(other))}, other
+    assert _lib.exported_symbols() == tuple(n for k in _lib.HEADERS for n in _lib.exported_symbols(k))
+    for ret, name, args in declared:
+        assert hasattr(raw, name), f'{name} declared in {_lib.HEADERS[key][0]} but not exported'
         f = getattr(lib, name)
+        names = [re.search(r'\w+$', a).group() for a in args]
+        types = [a.replace('const ', '')[:-len(n)].strip() for a, n in zip(args, names)]
+        assert len(set(names)) == len(names), name
+        if name.startswith('mr_'):
+            want_ret = ctypes.c_char_p if ret == 'const char *' else _SCALAR[ret]
+            want = [ctypes.c_void_p if '*' in t else _SCALAR[t] for t in types]
+            assert list(_lib.arg_names(name)) == (names[:-1] if names[-1:] == ['stream'] else names), name
+        else:                                                                                        # ext.h's symbols: typed pointers
+            want_ret = None if ret == 'void' else _SCALAR[ret]
+            want = [ctypes.POINTER(_SCALAR[t.replace('*', '').strip()]) if '*' in t else _SCALAR[t] for t in types]
         assert f.restype is want_ret, name
         assert list(f.argtypes or []) == want, name
-        assert len(set(names)) == len(names), name
-        assert names == (list(_lib.arg_names(name)) + ['stream'] if names and names[-1] == 'stream' else list(_lib.arg_names(name))), name
-        seen.append(name)
-    assert sorted(seen) == sorted(n for n in _lib.EXPORTED_SYMBOLS if n.startswith('mr_')) and len(seen) == 31
+    assert not _lib._stale()
+    so_time, real = os.path.getmtime(_lib.SO), os.path.getmtime
+    monkeypatch.setattr(os.path, 'getmtime', lambda f: so_time + 10 if f == _lib.header_path(key) else real(f))
+    assert _lib._stale()
 
 
 def test_pack_orders_named_arguments_as_the_abi_does():

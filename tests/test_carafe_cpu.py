@@ -1,8 +1,6 @@
 """The CARAFE op's torch restatement against the fp64 definition (tests/carafe_ref.py), the module's parameters, and the C ABI of the
 fused launches (include/monorun_carafe.h) as far as it goes without a GPU."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -98,38 +96,14 @@ def test_carafe_pack_module_parameters():
     assert x.grad is not None and small.content_encoder.weight.grad is not None
 
 
-def test_loader_binds_the_carafe_header(monkeypatch):
-    from monorun_amd import _lib
+def test_loader_binds_the_carafe_header():
+    """What is CARAFE's own; test_capi_and_host.py::test_loader_binds_every_header has what holds for every header."""
+    from monorun_amd import _lib, carafe
     lib = _lib.load()
-    assert _lib.CARAFE_EXPORTED_SYMBOLS == ('mr_carafe_pack_forward', 'mr_carafe_backward_workspace_bytes', 'mr_carafe_pack_backward')
-    protos = _lib.header_prototypes(_lib.CARAFE_HEADER)
-    assert [n for n, _, _ in protos] == list(_lib.CARAFE_EXPORTED_SYMBOLS)
-    others = (set(_lib.EXPORTED_SYMBOLS) | set(_lib.HEADS_EXPORTED_SYMBOLS) | set(_lib.TRAIN_EXPORTED_SYMBOLS) | set(_lib.TARGETS_EXPORTED_SYMBOLS)
-              | set(_lib.GLOBAL_EXPORTED_SYMBOLS))
-    assert not others & set(_lib.CARAFE_EXPORTED_SYMBOLS)
-    for h in (_lib.HEADER, _lib.HEADS_HEADER, _lib.TRAIN_HEADER, _lib.TARGETS_HEADER, _lib.GLOBAL_HEADER):
-        assert not {n for n, _, _ in _lib.header_prototypes(h)} & set(_lib.CARAFE_EXPORTED_SYMBOLS)
-    # the expected ctypes types from the header text, not by the loader's own mapping
-    src = re.sub(r'/\*.*?\*/', ' ', open(_lib.CARAFE_HEADER).read(), flags=re.S)
-    found = re.findall(r'^((?:const\s+)?\w+[\s\*]+)(mr_\w+)\s*\(([^)]*)\)\s*;', src, flags=re.M)
-    assert [name for _, name, _ in found] == list(_lib.CARAFE_EXPORTED_SYMBOLS)
-    scalar = {'int': ctypes.c_int, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t}
-    for ret, name, args in found:
-        args = [' '.join(a.split()) for a in args.split(',')]
-        want = [ctypes.c_void_p if '*' in a else scalar[a.replace('const ', '').rsplit(None, 1)[0]] for a in args]
-        f = getattr(lib, name)                                                                     # the library exports the symbol
-        assert f.restype is scalar[ret.strip()] and list(f.argtypes) == want, name
-        names = [re.search(r'\w+$', a).group() for a in args]
-        assert list(_lib.arg_names(name)) == (names[:-1] if names[-1] == 'stream' else names)
     assert len(lib.mr_carafe_pack_forward.argtypes) == 11 and len(lib.mr_carafe_pack_backward.argtypes) == 15
+    src = open(_lib.header_path('carafe')).read()
     assert '#define MR_CARAFE_CHUNK 32' in src and '#define MR_CARAFE_TILE 16' in src and '#define MR_CARAFE_MAX_KERNEL 7' in src
-    from monorun_amd import carafe
     assert (carafe.CHUNK, carafe.TILE, carafe.MAX_KERNEL) == (32, 16, 7) and ref.CHUNK == carafe.CHUNK
-    # the new header makes the library stale like the others
-    assert not _lib._stale()
-    so_time, real = os.path.getmtime(_lib.SO), os.path.getmtime
-    monkeypatch.setattr(os.path, 'getmtime', lambda f: so_time + 10 if f == _lib.CARAFE_HEADER else real(f))
-    assert _lib._stale()
 
 
 def test_entry_points_check_their_arguments_without_a_gpu():

@@ -16,7 +16,7 @@ KERNELS = {'gh_p_kernel': TILE_LDS, 'gh_h1_kernel': TILE_LDS, 'gh_h2_kernel': TI
 
 @pytest.mark.skipif(not have_hipcc(), reason='hipcc not installed')
 def test_global_head_kernels_compile_without_scratch_or_spills():
-    assert len(_lib.GLOBAL_EXPORTED_SYMBOLS) == 2 and TILE_LDS == 16896
+    assert len(_lib.exported_symbols('global')) == 2 and TILE_LDS == 16896
     kernels = kernel_resources()
     for k, lds in KERNELS.items():
         found = {name: r for name, r in kernels.items() if re.search(r'\d' + k + 'E', name)}          # _ZN12_GLOBAL__N_1<len><name>E...

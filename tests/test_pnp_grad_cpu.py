@@ -135,7 +135,7 @@ def test_invalid_combinations_raise_value_error():
 
 def test_backward_symbol_exported_and_argument_checks():
     from monorun_amd import _lib
-    assert 'mr_pnp_uncert_backward_batched' in _lib.EXPORTED_SYMBOLS
+    assert 'mr_pnp_uncert_backward_batched' in _lib.exported_symbols('pnp')
     lib = _lib.load()
     f = lib.mr_pnp_uncert_backward_batched
     nulls = lambda B: (None, None, None, None, None, None, 0, None, 1, None, None, 1, None, None, None, 0, None, None, None, B, 16, 0.5,

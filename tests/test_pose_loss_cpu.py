@@ -169,7 +169,7 @@ def test_head_construction_and_state_dict_unchanged():
 def test_iou_op_argument_checks_and_exported_symbol():
     from monorun_amd import _lib
     from monorun_amd.iou3d import bbox3d_overlaps_aligned
-    assert 'mr_bbox3d_overlaps_aligned' in _lib.EXPORTED_SYMBOLS
+    assert 'mr_bbox3d_overlaps_aligned' in _lib.exported_symbols('pnp')
     lib = _lib.load()
     f = lib.mr_bbox3d_overlaps_aligned
     args = lambda n=4, stride=7, crit=-1, z=1, flags=0: (None, stride, None, 7, n, crit, z, 1.0, flags, None, None, None)

@@ -5,7 +5,6 @@ restatement of monorun_roi_head.py:536-550.  No GPU."""
 import ctypes
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -187,32 +186,14 @@ def test_cross_entropy_loss_is_bce_with_logits():
     torch.testing.assert_close(built(pred, target), raw.mean())
 
 
-def test_loader_binds_the_heads_header(monkeypatch):
+def test_loader_binds_the_heads_header():
+    """What is the score head's own; test_capi_and_host.py::test_loader_binds_every_header has what holds for every header."""
     from monorun_amd import _lib
-    lib = _lib.load()
-    assert _lib.HEADS_EXPORTED_SYMBOLS == ('mr_score_head_forward',)
-    assert len(_lib.EXPORTED_SYMBOLS) == 34 and 'mr_score_head_forward' not in _lib.EXPORTED_SYMBOLS
-    assert [n for n, _, _ in _lib.header_prototypes()] == [n for n, _, _ in _lib.header_prototypes(_lib.HEADER)]      # the default is unchanged
-    protos = _lib.header_prototypes(_lib.HEADS_HEADER)
-    assert [n for n, _, _ in protos] == list(_lib.HEADS_EXPORTED_SYMBOLS)
-    # the expected ctypes types from the header text, not by the loader's own mapping
-    src = re.sub(r'/\*.*?\*/', ' ', open(_lib.HEADS_HEADER).read(), flags=re.S)
-    (ret, name, args), = re.findall(r'^((?:const\s+)?\w+[\s\*]+)(mr_\w+)\s*\(([^)]*)\)\s*;', src, flags=re.M)
-    scalar = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64}
-    args = [a.strip() for a in args.split(',')]
-    want = [ctypes.c_void_p if '*' in a else scalar[a.replace('const ', '').rsplit(None, 1)[0]] for a in args]
-    f = lib.mr_score_head_forward
-    assert f.restype is ctypes.c_int and list(f.argtypes) == want and len(want) == 19
-    names = [re.search(r'\w+$', a).group() for a in args]
-    assert names[-1] == 'stream' and list(_lib.arg_names('mr_score_head_forward')) == names[:-1]
-    assert _lib.pack('mr_score_head_forward', **{n: k for k, n in enumerate(names[:-1])}) == list(range(18))
+    names = _lib.arg_names('mr_score_head_forward')
+    assert len(_lib.load().mr_score_head_forward.argtypes) == 19 and len(names) == 18                # stream last, not among the names
+    assert _lib.pack('mr_score_head_forward', **{n: k for k, n in enumerate(names)}) == list(range(18))
     assert _lib.arg_names('mr_uncert_projection')[0] == 'coords_3d'                                  # both headers answer by name
-    assert '#define MR_SCORE_SIGMOID 0x1' in src and _lib.MR_SCORE_SIGMOID == 1
-    # the new header makes the library stale like the old one
-    assert not _lib._stale()
-    so_time, real = os.path.getmtime(_lib.SO), os.path.getmtime
-    monkeypatch.setattr(os.path, 'getmtime', lambda f: so_time + 10 if f == _lib.HEADS_HEADER else real(f))
-    assert _lib._stale()
+    assert '#define MR_SCORE_SIGMOID 0x1' in open(_lib.header_path('heads')).read() and _lib.MR_SCORE_SIGMOID == 1
 
 
 def test_entry_point_rejects_bad_arguments_without_a_gpu():
