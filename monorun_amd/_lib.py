@@ -39,16 +39,30 @@ HEADERS = {
     'global': ('monorun_global.h', ('mr_global_head_mc_workspace_bytes', 'mr_global_head_mc_forward')),                # section 16
     'carafe': ('monorun_carafe.h', ('mr_carafe_pack_forward', 'mr_carafe_backward_workspace_bytes', 'mr_carafe_pack_backward')),   # section 17
 }
+# The headers added since the table above was pinned to its six rows (tests/test_capi_and_host.py): the same form, walked after it by
+# `_stale`, `load` and the prototypes; `exported_symbols()` without a key stays the list of ``HEADERS``.
+EXTRA_HEADERS = {
+    'roi': ('monorun_roi.h', ('mr_roi_extract_forward', 'mr_roi_extract_backward')),                                   # section 18
+}
+
+
+def _table(key):
+    return HEADERS[key] if key in HEADERS else EXTRA_HEADERS[key]
+
+
+def header_keys():
+    """The keys of every header: ``HEADERS``, then ``EXTRA_HEADERS``."""
+    return tuple(HEADERS) + tuple(EXTRA_HEADERS)
 
 
 def header_path(key):
-    """The file of one of the headers of ``HEADERS``."""
-    return os.path.join(INCLUDE, HEADERS[key][0])
+    """The file of one of the headers of ``HEADERS`` or ``EXTRA_HEADERS``."""
+    return os.path.join(INCLUDE, _table(key)[0])
 
 
 def exported_symbols(key=None):
-    """The pinned entry points of one header, or of all of them in table order."""
-    return HEADERS[key][1] if key is not None else tuple(n for _, names in HEADERS.values() for n in names)
+    """The pinned entry points of one header (of either table), or of all those of ``HEADERS`` in table order."""
+    return _table(key)[1] if key is not None else tuple(n for _, names in HEADERS.values() for n in names)
 
 
 MR_F32, MR_F16, MR_F64, MR_BF16 = 0, 1, 2, 3
@@ -73,7 +87,7 @@ def _stale():
         return True
     t = os.path.getmtime(SO)
     csrc = os.path.join(_HERE, 'csrc')
-    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [header_path(k) for k in HEADERS]
+    deps = glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.inc')) + [header_path(k) for k in header_keys()]
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -105,7 +119,7 @@ def header_prototypes(path=None):
 
 
 def _all_prototypes():
-    return [p for k in HEADERS for p in header_prototypes(header_path(k))]
+    return [p for k in header_keys() for p in header_prototypes(header_path(k))]
 
 
 _CTYPES = {'int': ctypes.c_int, 'float': ctypes.c_float, 'double': ctypes.c_double, 'size_t': ctypes.c_size_t, 'int64_t': ctypes.c_int64}

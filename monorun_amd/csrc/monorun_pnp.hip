@@ -22,6 +22,7 @@
 #include "monorun_targets.h"
 #include "monorun_global.h"
 #include "monorun_carafe.h"
+#include "monorun_roi.h"
 
 namespace {
 
@@ -106,6 +107,7 @@ constexpr size_t kNocLds = sizeof(double) * (2 * 4 * kRedN + 2 * 40);     // red
 #include "score_head_kernel.inc"
 #include "global_head_kernel.inc"
 #include "carafe_kernel.inc"
+#include "roi_extract_kernel.inc"
 #include "consumers_kernel.inc"
 #include "host_launch.inc"
 
@@ -127,6 +129,7 @@ extern "C" {
 #include "targets_abi.inc"
 #include "global_abi.inc"
 #include "carafe_abi.inc"
+#include "roi_extract_abi.inc"
 #include "debug_abi.inc"
 
 }  // extern "C"

@@ -62,6 +62,52 @@ __device__ __forceinline__ float roi_align_avg_bin(const float *in, int H, int W
     return acc / count;
 }
 
+// The same rules in parts, for the multi-level extractor (roi_extract_kernel.inc), which computes a RoI's sample geometry once and reuses it for
+// every channel, and transposes it in its backward: roi_bilinear = roi_axis_tap in y and in x + roi_blend; roi_align_avg_bin = roi_geom +
+// roi_sample_coord + that.  Operation for operation the arithmetic above (tests/test_gpu_roi_extract.py compares the two bit for bit).  The two
+// functions above keep their own text: expressed through the parts they moved the code of 17 tuned kernels (the fused PnP instantiations, K2,
+// roi_align_avg_kernel; tools/isa_diff.sh), as the folds of HISTORY.md round 12 did.
+// One axis of a bilinear sample (the y rule and the x rule are the same): `dead` when the coordinate is more than a pixel outside [0, size);
+// else the two taps lo, hi (equal in the last row / column) and their weights h = 1 - l, l.
+struct RoiTap { int lo, hi; float l, h; };
+__device__ __forceinline__ bool roi_axis_tap(float v, int size, RoiTap &t) {
+#pragma clang fp contract(off)
+    if (v < -1.0f || v > (float)size) return true;
+    if (v <= 0.0f) v = 0.0f;
+    t.lo = (int)v;
+    if (t.lo >= size - 1) { t.hi = t.lo = size - 1; v = (float)t.lo; } else t.hi = t.lo + 1;
+    t.l = v - (float)t.lo; t.h = 1.0f - t.l;
+    return false;
+}
+// the four taps of one sample of one channel, blended: the order of the products and of the sum is the definition
+__device__ __forceinline__ float roi_blend(const float *in, int W, const RoiTap &ty, const RoiTap &tx) {
+#pragma clang fp contract(off)
+    const float v1 = in[ty.lo * W + tx.lo], v2 = in[ty.lo * W + tx.hi], v3 = in[ty.hi * W + tx.lo], v4 = in[ty.hi * W + tx.hi];
+    const float w1 = ty.h * tx.h, w2 = ty.h * tx.l, w3 = ty.l * tx.h, w4 = ty.l * tx.l;
+    return w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4;
+}
+// The per-RoI terms of the pooling; roi = x1 y1 x2 y2 already multiplied by spatial_scale.  gh, gw: the sample grid of a bin (<= 0: no
+// sample), count the divisor.  At sampling_ratio 0 the grid is (int)ceilf(rh / out_h): the caller bounds it where the RoI is not trusted.
+struct RoiGeom { float sw, sh, rw, rh, bw, bh, count; int gw, gh; };
+__device__ __forceinline__ RoiGeom roi_geom(float x1, float y1, float x2, float y2, int out_h, int out_w, int sampling_ratio, int aligned) {
+#pragma clang fp contract(off)
+    RoiGeom g;
+    const float off = aligned ? 0.5f : 0.0f;
+    g.sw = x1 - off; g.sh = y1 - off;
+    g.rw = (x2 - off) - g.sw; g.rh = (y2 - off) - g.sh;
+    if (!aligned) { g.rw = fmaxf(g.rw, 1.0f); g.rh = fmaxf(g.rh, 1.0f); }
+    g.bh = g.rh / (float)out_h; g.bw = g.rw / (float)out_w;
+    g.gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(g.rh / (float)out_h);
+    g.gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(g.rw / (float)out_w);
+    g.count = (float)max(g.gh * g.gw, 1);
+    return g;
+}
+// the coordinate of sample i of the g of bin p along one axis (start: sh or sw, bin: bh or bw)
+__device__ __forceinline__ float roi_sample_coord(float start, float bin, int p, int i, int g) {
+#pragma clang fp contract(off)
+    return start + (float)p * bin + ((float)i + 0.5f) * bin / (float)g;
+}
+
 // exp / log of the istd chain, SPECIFIED (not library calls): the decoded istd feeds a bit-exact threshold (the istd inlier
 // mask, pnp_uncert_cpu.py:164-168), so its last bit must not depend on which libm / device library computed it.  Classical
 // single-precision algorithms (Cephes expf / logf: Cody-Waite reduction with the two-part ln 2, degree-5 / degree-8
