@@ -29,8 +29,8 @@ __device__ __forceinline__ float rotated_iou(const NmsBox &a, const NmsBox &b) {
     float ov = 0.0f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        ov += edge_inside_area_t<float, true>(ax[i], ay[i], ax[(i + 1) & 3] - ax[i], ay[(i + 1) & 3] - ay[i], bx, by);
-        ov += edge_inside_area_t<float, false>(bx[i], by[i], bx[(i + 1) & 3] - bx[i], by[(i + 1) & 3] - by[i], ax, ay);
+        ov += edge_inside_area_t<float, true>(ax[i], ay[i], ax[(i + 1) & 3], ay[(i + 1) & 3], bx, by);
+        ov += edge_inside_area_t<float, false>(bx[i], by[i], bx[(i + 1) & 3], by[(i + 1) & 3], ax, ay);
     }
     ov = fmaxf(ov, 0.0f);
     return ov / fmaxf(a.area + b.area - ov, 1e-8f);

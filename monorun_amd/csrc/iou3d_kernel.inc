@@ -10,9 +10,10 @@
 // camera boxes), z_center the height centre (1.0: the coordinate is the bottom of the box, y pointing down).
 //
 // BEV area: eval_rotated_intersection (kitti_eval_kernel.inc), the corner convention of rbbox_to_corners, inputs rounded to fp32,
-// result rounded to fp32 — the value the numba kernel stores.  The box is the first argument, as in the aligned numba kernel.  Its
-// UNFUSED form (edge dot products not contracted) makes identical boxes give their area: the numba kernel is degenerate there (1/3 or
-// 0 of it), as the KITTI evaluator's fused form is; elsewhere the two forms differ by rounding only.
+// result rounded to fp32 — the value the numba kernel stores.  The box is the first argument, as in the aligned numba kernel.  The
+// routine's one rule (edge_inside_area_t): coincident edges of the same direction are counted once, coincident edges of opposite direction
+// never, decided unfused — identical boxes give their area, boxes that only touch give 0.  The numba kernel is degenerate on identical
+// boxes (1/3 or 0 of the area).
 //
 // Height rules (flags):
 //   default, "reference":      max_z = min(box_top, qbox_top) — what bev_to_box3d_overlaps_aligned_torch computes (:145, torch.min),
@@ -35,7 +36,7 @@ __global__ void __launch_bounds__(256) bbox3d_overlaps_aligned_kernel(const floa
     const int a0 = z_axis == 0 ? 1 : 0, a1 = z_axis == 2 ? 1 : 2;
     const double bb[5] = { (double)b[a0], (double)b[a1], (double)b[a0 + 3], (double)b[a1 + 3], (double)b[6] };
     const double qb[5] = { (double)q[a0], (double)q[a1], (double)q[a0 + 3], (double)q[a1 + 3], (double)q[6] };
-    const float rinc = (float)eval_rotated_intersection<true>(bb, qb);
+    const float rinc = (float)eval_rotated_intersection(bb, qb);
     // height and volume composition (bbox3d_iou_calculator.py:140-163)
     const float up = (float)(1.0 - (double)z_center);     // the Python scalar (1 - z_center), rounded to the tensor's fp32
     const float bz = b[z_axis], bh = b[z_axis + 3], qz = q[z_axis], qh = q[z_axis + 3];

@@ -5,7 +5,9 @@
 // three embarrassingly parallel HIP kernels over flat, offset-indexed arrays (HBM-bound integer/compare work):
 //   kitti_overlap_kernel   one thread per (detection, label) pair of the SAME image  (eval.py:84-158, rotate_iou.py:256-281)
 //                          — the reference computes whole cross-image "part" matrices and slices the diagonal blocks out
-//                          (eval.py:341-416); only the diagonal blocks are computed here
+//                          (eval.py:341-416); only the diagonal blocks are computed here.  On identical boxes the rotated
+//                          overlap is 1, a deliberate departure from the numba kernel's value there (1/3 or 0 of the area):
+//                          edge_inside_area_t below
 //   kitti_match_kernel     one thread per (class x difficulty x overlap "combo", [threshold,] image): the sequential greedy
 //                          assignment compute_statistics_jit (eval.py:161-279)
 //   kitti_reduce_kernel    one thread per (combo, threshold): ordered sum over images (fused_compute_statistics, eval.py:291-338)
@@ -30,24 +32,57 @@ __device__ __forceinline__ T dot2_unfused(T a, T b, T c, T d) {
 #pragma clang fp contract(off)
     return a * b + c * d;
 }
+// z of (ux, uy) x (vx, vy), likewise
+template <typename T>
+__device__ __forceinline__ T cross2_unfused(T ux, T uy, T vx, T vy) { return dot2_unfused(ux, vy, -uy, vx); }
 
-// length-weighted boundary integral of the part of segment p->p+d that lies inside the convex CCW polygon q
-// (Cyrus-Beck parametric clipping, no dynamic arrays); CLOSED selects >= (boundary counts) or > (it does not),
-// so that an edge shared by both rectangles is counted exactly once.  Any scalar type (float: the NMS).  UNFUSED (the 3-D IoU, iou3d_kernel.inc): the
-// two dot products are not contracted, so that an edge lying on the other box's edge (identical boxes) gives den == 0 and f0 == 0
-// exactly and the shared edge is counted once; the default (the KITTI evaluator) compiles as it always has.
-template <typename T, bool CLOSED, bool UNFUSED = false>
-__device__ __forceinline__ T edge_inside_area_t(T px, T py, T dx, T dy, const T (&qx)[4], const T (&qy)[4]) {
+__device__ __forceinline__ float t_abs(float a) { return fabsf(a); }
+__device__ __forceinline__ double t_abs(double a) { return fabs(a); }
+template <typename T> struct CollinearTol;      // 64 ulp: the corners carry a few ulp of their box's size each, the cross products some more
+template <> struct CollinearTol<float> { static constexpr float value = 64.0f * 1.1920929e-07f; };
+template <> struct CollinearTol<double> { static constexpr double value = 64.0 * 2.220446049250313e-16; };
+
+// Whether segment p -> r and edge a -> b lie on one line: each one's two ends within tol of the other's line.  f0 is p against the
+// edge's line.  The four cross products are the same numbers when segment and edge change places.
+template <typename T>
+__device__ __forceinline__ bool on_one_line(T px, T py, T rx, T ry, T ax, T ay, T bx, T by, T f0, T tol) {
+    const T ex = bx - ax, ey = by - ay, dx = rx - px, dy = ry - py;
+    const T f1 = cross2_unfused(ex, ey, rx - ax, ry - ay);                                                       // r against the edge's line
+    const T g0 = cross2_unfused(dx, dy, ax - px, ay - py), g1 = cross2_unfused(dx, dy, bx - px, by - py);        // a, b against the segment's
+    return t_max(t_max(t_abs(f0), t_abs(f1)), t_max(t_abs(g0), t_abs(g1))) <= tol;
+}
+
+// length-weighted boundary integral of the part of segment p -> r that lies inside the convex CCW polygon q (Cyrus-Beck parametric
+// clipping, no dynamic arrays).  Any scalar type (float: the NMS, double: the evaluator and the 3-D IoU).  The intersection's
+// boundary is the first rectangle's segments inside the second (CLOSED) plus the second's inside the first (not CLOSED), so a stretch
+// of boundary that both rectangles have must come from exactly one of the two calls that meet it.  One rule decides that, for a
+// segment and an edge of q that lie on one line:
+//   - CLOSED, and the segment runs the way the edge runs (the interiors are on the same side: identical boxes, a box inside the other
+//     on a common edge): the edge does not clip the segment, so it counts;
+//   - CLOSED, and it runs the other way (the interiors are on opposite sides: boxes that only touch): it does not count;
+//   - not CLOSED: it does not count.
+// So coincident edges of the same direction are counted once and those of opposite direction never.  "On one line" means that each
+// one's two ends are within CollinearTol of the other's line: the four cross products against the product of the two L1 lengths.
+// The test reads the same four numbers whichever of the two is the segment, so both calls decide alike, also for edges that coincide
+// only to the rounding of their corners (turned boxes with a common centre line), where the signs of f0 and den are noise.
+// Every product here is rounded operation by operation: as FMAs, den of an edge against itself is the rounding residue of a product
+// instead of 0, and the result would rest on what the compiler contracts.
+template <typename T, bool CLOSED>
+__device__ __forceinline__ T edge_inside_area_t(T px, T py, T rx, T ry, const T (&qx)[4], const T (&qy)[4]) {
+    const T dx = rx - px, dy = ry - py;
     T t0 = T(0), t1 = T(1);
     bool empty = false;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const T ax = qx[e], ay = qy[e], bx = qx[(e + 1) & 3], by = qy[(e + 1) & 3];
-        const T nx = -(by - ay), ny = bx - ax;                      // inward normal of a CCW edge
-        T f0, den;
-        if constexpr (UNFUSED) { f0 = dot2_unfused(nx, px - ax, ny, py - ay); den = dot2_unfused(nx, dx, ny, dy); }
-        else { f0 = nx * (px - ax) + ny * (py - ay); den = nx * dx + ny * dy; }
-        if (den > T(0)) t0 = t_max(t0, -f0 / den);
+        const T ex = bx - ax, ey = by - ay;                         // (-ey, ex) is the inward normal of a CCW edge
+        const T f0 = cross2_unfused(ex, ey, px - ax, py - ay), den = cross2_unfused(ex, ey, dx, dy);          // p against the edge's line
+        const T tol = CollinearTol<T>::value * ((t_abs(ex) + t_abs(ey)) * (t_abs(dx) + t_abs(dy)));
+        // den is f1 - f0 but for rounding, far below tol: only a nearly parallel pair can be on one line (|den| is the same in both calls)
+        if (t_abs(den) <= T(3) * tol && tol > T(0) && on_one_line(px, py, rx, ry, ax, ay, bx, by, f0, tol)) {
+            if (!CLOSED || dot2_unfused(dx, ex, dy, ey) < T(0)) empty = true;
+        }
+        else if (den > T(0)) t0 = t_max(t0, -f0 / den);
         else if (den < T(0)) t1 = t_min(t1, -f0 / den);
         else if (CLOSED ? (f0 < T(0)) : (f0 <= T(0))) empty = true;
     }
@@ -67,7 +102,6 @@ __device__ __forceinline__ void eval_corners(const double (&b)[5], double ox, do
     if (hx * hy < 0.0) { const double tx = px[1], ty = py[1]; px[1] = px[3]; py[1] = py[3]; px[3] = tx; py[3] = ty; }
 }
 
-template <bool UNFUSED = false>
 __device__ __forceinline__ double eval_rotated_intersection(const double (&a)[5], const double (&b)[5]) {
     double ax[4], ay[4], bx[4], by[4];
     eval_corners(a, a[0], a[1], ax, ay);
@@ -75,8 +109,8 @@ __device__ __forceinline__ double eval_rotated_intersection(const double (&a)[5]
     double ov = 0.0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        ov += edge_inside_area_t<double, true, UNFUSED>(ax[i], ay[i], ax[(i + 1) & 3] - ax[i], ay[(i + 1) & 3] - ay[i], bx, by);
-        ov += edge_inside_area_t<double, false, UNFUSED>(bx[i], by[i], bx[(i + 1) & 3] - bx[i], by[(i + 1) & 3] - by[i], ax, ay);
+        ov += edge_inside_area_t<double, true>(ax[i], ay[i], ax[(i + 1) & 3], ay[(i + 1) & 3], bx, by);
+        ov += edge_inside_area_t<double, false>(bx[i], by[i], bx[(i + 1) & 3], by[(i + 1) & 3], ax, ay);
     }
     return fmax(ov, 0.0);
 }

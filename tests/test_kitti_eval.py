@@ -204,6 +204,124 @@ def test_gpu_eval_edge_cases():
     assert line == '3d   AP:{:.2f}, {:.2f}, {:.2f}'.format(*want[0])
 
 
+def _crowded_annos(counts, seed=5):
+    """One image per entry of counts with that many detections and 6 to 8 labels (5 to 7 objects apart from each other and one
+    DontCare region), for the matching kernel's `taken` words beyond the first.  Every object has one true match, a slightly jittered
+    copy with a score below every other detection's, so that the descending sort puts the true matches last.  Object 0's match is
+    there twice with two scores and object 1's twice with one score (equal overlaps on one label, a tie).  The rest are false positives
+    away from the labels in the BEV plane, half of them with scores on a 0.05 grid (ties), a few inside the DontCare region."""
+    rng = np.random.default_rng(seed)
+    f32 = lambda v, shape: np.asarray(v, np.float32).reshape(shape)
+    gts, dts = [], []
+    for nd in counts:
+        n_obj = int(rng.integers(5, 8))
+        g = dict(name=[], truncated=[], occluded=[], alpha=[], bbox=[], dimensions=[], location=[], rotation_y=[])
+        d = dict(name=[], alpha=[], bbox=[], dimensions=[], location=[], rotation_y=[], score=[])
+
+        def add_det(nm, loc, dims, ry, bbox, score):
+            d['name'].append(nm); d['alpha'].append(ry - np.arctan2(loc[0], loc[2] + 0.27)); d['bbox'].append(bbox)
+            d['dimensions'].append(dims); d['location'].append(loc); d['rotation_y'].append(ry); d['score'].append(score)
+        for i in range(n_obj):
+            nm = ('Car', 'Pedestrian', 'Car', 'Cyclist', 'Van', 'Car', 'Pedestrian')[i]
+            dims = np.array(syn._KITTI_DIMS[nm]) * rng.uniform(0.9, 1.1, 3)
+            loc = np.array([(i - 3) * 2.2 + rng.uniform(-0.2, 0.2), rng.uniform(1.4, 1.9), 12 + 4 * i + rng.uniform(-0.2, 0.2)])
+            ry = rng.uniform(-np.pi, np.pi)
+            bbox, trunc = syn._kitti_bbox(loc, dims, ry)
+            g['name'].append(nm); g['truncated'].append(trunc); g['occluded'].append(int(rng.choice([0, 0, 1, 2]))); g['alpha'].append(ry - np.arctan2(loc[0], loc[2]))
+            g['bbox'].append(bbox); g['dimensions'].append(dims); g['location'].append(loc); g['rotation_y'].append(ry)
+            det = ('Car' if nm == 'Van' else nm, loc + rng.normal(0, 0.05, 3), dims * rng.uniform(0.98, 1.02, 3), ry + rng.normal(0, 0.02),
+                   bbox + rng.normal(0, 0.5, 4))
+            add_det(*det, rng.uniform(0.02, 0.05))
+            if i == 0:
+                add_det(*det, 0.015)
+            elif i == 1:
+                add_det(*det, d['score'][-1])
+        x1, y1, w, h = rng.uniform(100, 900), rng.uniform(120, 200), 120.0, 80.0
+        g['name'].append('DontCare'); g['truncated'].append(-1); g['occluded'].append(-1); g['alpha'].append(-10)
+        g['bbox'].append(np.array([x1, y1, x1 + w, y1 + h])); g['dimensions'].append(np.full(3, -1.0))
+        g['location'].append(np.full(3, -1000.0)); g['rotation_y'].append(-10)
+        k = 0
+        while len(d['name']) < nd:
+            nm = ('Car', 'Pedestrian', 'Cyclist')[int(rng.integers(3))]
+            dims = np.array(syn._KITTI_DIMS[nm]) * rng.uniform(0.9, 1.1, 3)
+            z = rng.uniform(25, 75)
+            loc = np.array([rng.choice([-1.0, 1.0]) * rng.uniform(11, max(11.5, 0.5 * z)), rng.uniform(1.4, 1.9), z])
+            ry = rng.uniform(-np.pi, np.pi)
+            bbox, _t = syn._kitti_bbox(loc, dims, ry)
+            if k % 16 == 5:                                    # inside the DontCare region, tall enough to count at every difficulty
+                bbox = np.array([x1 + 10, y1 + 10, x1 + 60, y1 + 70]) + rng.uniform(0, 8, 4)
+            add_det(nm, loc, dims, ry, bbox, np.round(rng.uniform(0.1, 0.9) * 20) / 20 if k % 2 else rng.uniform(0.1, 0.9))
+            k += 1
+        ng = len(g['name'])
+        gts.append(dict(name=np.array(g['name'], dtype='<U16'), truncated=f32(g['truncated'], (ng,)), occluded=f32(g['occluded'], (ng,)),
+                        alpha=f32(g['alpha'], (ng,)), bbox=f32(g['bbox'], (ng, 4)), dimensions=f32(g['dimensions'], (ng, 3)),
+                        location=f32(g['location'], (ng, 3)), rotation_y=f32(g['rotation_y'], (ng,)), score=np.zeros(ng, np.float32)))
+        order = np.argsort(-f32(d['score'], (nd,)), kind='stable')
+        dts.append(dict(name=np.array(d['name'], dtype='<U16')[order], truncated=np.full(nd, -1, np.int8), occluded=np.full(nd, -1, np.int8),
+                        alpha=f32(d['alpha'], (nd,))[order], bbox=f32(d['bbox'], (nd, 4))[order], dimensions=f32(d['dimensions'], (nd, 3))[order],
+                        location=f32(d['location'], (nd, 3))[order], rotation_y=f32(d['rotation_y'], (nd,))[order], score=f32(d['score'], (nd,))[order]))
+    return gts, dts
+
+
+@pytest.fixture(scope='module')
+def crowded():
+    """(gts, dts, the oracle's overlap blocks per metric) of the crowded set: detection counts at and around one 64-bit word of the
+    matching kernel's `taken` set and at its capacity (kEvalMaxDet = 512)."""
+    gts, dts = _crowded_annos((63, 64, 65, 512))
+    return gts, dts, {m: [ke.overlaps_one_image(d, g, m) for d, g in zip(dts, gts)] for m in (0, 1, 2)}
+
+
+def test_crowded_set_is_what_it_claims(crowded):
+    gts, dts, ovs = crowded
+    assert [len(d['name']) for d in dts] == [63, 64, 65, 512] and all(6 <= len(g['name']) <= 8 for g in gts)
+    for g, d, o0, o2 in zip(gts, dts, ovs[0], ovs[2]):
+        nd, obj = len(d['name']), np.flatnonzero(g['name'] != 'DontCare')
+        assert np.all(np.diff(d['score']) <= 0)
+        assert len(np.unique(d['score'])) <= nd - 10                                   # ties in score
+        for o in (o0, o2):                                                             # the true matches come last: word 7 of the 512
+            assert (o[:, obj].argmax(0) >= nd - 9).all() and (o[:, obj].max(0) > 0.5).all()
+            for i in (0, 1):                                                           # two detections with equal overlap on one label
+                assert (o[:, obj[i]] == o[:, obj[i]].max()).sum() == 2
+        assert (o2[:nd - 9][:, obj] == 0).all()                                        # the false positives are clear of the labels (BEV)
+        both = np.flatnonzero(o2[:, obj[1]] == o2[:, obj[1]].max())
+        assert d['score'][both[0]] == d['score'][both[1]]
+    assert min(int(o.argmax(0).min()) for o in (ovs[0][3][:, :-1], ovs[2][3][:, :-1])) >= 448
+
+
+@pytest.mark.gpu
+def test_gpu_matching_beyond_one_taken_word(crowded):
+    """kitti_match_kernel keeps its `taken` set in eight 64-bit words: 63, 64, 65 and 512 detections in an image, the matches of the
+    largest in the last word."""
+    from monorun_amd import evaluation as ev
+    gts, dts, ovs = crowded
+    for metric in (0, 1, 2):
+        blocks, _, n_rows, n_cols = ev.calculate_iou_partly(dts, gts, metric)
+        assert [b.shape for b in blocks] == [(len(d['name']), len(g['name'])) for d, g in zip(dts, gts)]
+        assert n_rows.tolist() == [63, 64, 65, 512] and n_cols.tolist() == [len(g['name']) for g in gts]
+        for b, o in zip(blocks, ovs[metric]):
+            if metric == 0:
+                np.testing.assert_array_equal(b, o)                    # bit-exact (float32 arithmetic, same operation order)
+            else:
+                assert np.abs(b - o).max() <= 1e-6                     # fp64 clipping on both sides, rounded to float32
+    mo = ke.KITTI_MIN_OVERLAPS[:, :, [0, 1, 2]]
+    for metric in (0, 2):
+        a = ev.eval_class(gts, dts, [0, 1, 2], [0, 1, 2], metric, mo, compute_aos=(metric == 0))
+        b = ke.eval_class(gts, dts, [0, 1, 2], [0, 1, 2], metric, mo, compute_aos=(metric == 0))
+        assert (b['precision'] > 0).sum() > 20 and np.nanmax(b['recall']) > 0.5
+        for k in ('precision', 'recall', 'orientation'):
+            np.testing.assert_allclose(a[k], b[k], rtol=0, atol=1e-12, equal_nan=True, err_msg=f'{metric} {k}')
+
+
+@pytest.mark.gpu
+def test_gpu_matching_refuses_more_than_its_capacity():
+    """513 detections in one image: the binding raises MR_ERR_UNSUPPORTED (the host refuses before the matching kernel is launched)."""
+    from monorun_amd import evaluation as ev
+    gts, dts = _crowded_annos((63, 513))
+    mo = ke.KITTI_MIN_OVERLAPS[:, :, [0, 1, 2]]
+    with pytest.raises(RuntimeError, match=r'unsupported configuration .*code '):
+        ev.eval_class(gts, dts, [0], [0, 1, 2], 2, mo)
+
+
 def test_kitti_file_io_roundtrip(tmp_path):
     """open_label_file / open_calib_file / parse_ann_info (kitti3d_dataset.py:40-56,116-178) on files written in the KITTI
     format, and result files read back as labels."""
