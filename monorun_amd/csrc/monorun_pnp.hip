@@ -23,6 +23,7 @@
 #include "monorun_global.h"
 #include "monorun_carafe.h"
 #include "monorun_roi.h"
+#include "monorun_proposals.h"
 
 namespace {
 
@@ -108,6 +109,7 @@ constexpr size_t kNocLds = sizeof(double) * (2 * 4 * kRedN + 2 * 40);     // red
 #include "global_head_kernel.inc"
 #include "carafe_kernel.inc"
 #include "roi_extract_kernel.inc"
+#include "proposals_kernel.inc"
 #include "consumers_kernel.inc"
 #include "host_launch.inc"
 
@@ -130,6 +132,7 @@ extern "C" {
 #include "global_abi.inc"
 #include "carafe_abi.inc"
 #include "roi_extract_abi.inc"
+#include "proposals_abi.inc"
 #include "debug_abi.inc"
 
 }  // extern "C"
