@@ -49,6 +49,7 @@ EXTRA_HEADERS = {
 # `exported_symbols(key)` walk all three tables (``all_header_keys``); `header_keys()` and a bare `exported_symbols()` stay what they were.
 LATER_HEADERS = {
     'proposals': ('monorun_proposals.h', ('mr_proposal_decode', 'mr_nms_workspace_bytes', 'mr_nms_grouped')),        # section 19
+    'bbox': ('monorun_bbox.h', ('mr_bbox_head_rank', 'mr_bbox_head_select', 'mr_bbox_head_workspace_bytes', 'mr_bbox_head_detect')),   # section 20
 }
 
 

@@ -24,6 +24,7 @@
 #include "monorun_carafe.h"
 #include "monorun_roi.h"
 #include "monorun_proposals.h"
+#include "monorun_bbox.h"
 
 namespace {
 
@@ -110,6 +111,7 @@ constexpr size_t kNocLds = sizeof(double) * (2 * 4 * kRedN + 2 * 40);     // red
 #include "carafe_kernel.inc"
 #include "roi_extract_kernel.inc"
 #include "proposals_kernel.inc"
+#include "bbox_head_kernel.inc"
 #include "consumers_kernel.inc"
 #include "host_launch.inc"
 
@@ -133,6 +135,7 @@ extern "C" {
 #include "carafe_abi.inc"
 #include "roi_extract_abi.inc"
 #include "proposals_abi.inc"
+#include "bbox_head_abi.inc"
 #include "debug_abi.inc"
 
 }  // extern "C"
