@@ -392,9 +392,12 @@ int mr_roi_align_avg(const float *input, const float *rois, int K, int C, int H,
  *   boxes_xyxyr (total,5) f32 [x1, y1, x2, y2, ry] (xywhr2xyxyr, :657-677), scores (total) f32,
  *   offsets (groups+1) i32: group g owns rows [offsets[g], offsets[g+1]) (one group per class), max_group =
  *   largest group size (<= 512).  A box is suppressed when its rotated IoU with an already kept, higher
- *   scoring box of its group exceeds thr (score ties: lower index first).
- *   keep (total) i64: kept indices LOCAL to the group, descending score, written at keep[offsets[g] ...];
- *   num_keep (groups) i32.
+ *   scoring box of its group exceeds thr (score ties: lower index first).  The order is total: non-NaN scores before
+ *   NaN scores, non-NaN descending (+inf first, -inf last), equal scores and NaN scores by ascending index — NaN LAST,
+ *   unlike torch.sort(descending=True).  A box of zero area or with a NaN coordinate has IoU 0 with every box.
+ *   keep (total) i64: kept indices LOCAL to the group, in that order, written at keep[offsets[g] ...]; entries of a
+ *   group's slot beyond its num_keep are not written.  num_keep (groups) i32 (0 for an empty group).
+ *   max_group > 512: MR_ERR_UNSUPPORTED, nothing written.
  */
 int mr_nms_bev_batched(const float *boxes_xyxyr, const float *scores, const int32_t *offsets, int groups, int max_group,
                        float thr, int64_t *keep, int32_t *num_keep, void *stream);

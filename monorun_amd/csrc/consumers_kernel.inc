@@ -19,9 +19,16 @@ __global__ void __launch_bounds__(256) roi_align_avg_kernel(const float *in, con
 // suppression of IoU > thr).  One workgroup per class group (n <= kNmsMax boxes).
 constexpr int kNmsMax = 512;
 
+#define MR_NMS_FN __device__ __forceinline__
+#include "nms_order.inc"
+#undef MR_NMS_FN
+
 struct NmsBox { float cx, cy; float px[4], py[4]; float area; };   // CCW corners relative to nothing (absolute)
 
 __device__ __forceinline__ float rotated_iou(const NmsBox &a, const NmsBox &b) {
+    // a box of zero area (a segment, a point) meets nothing in a set of positive area: IoU 0.  Its zero-length edges clip nothing, so
+    // the boundary sum below would count the other box whole.  A NaN area (a NaN coordinate) compares false: IoU 0 as well.
+    if (!(a.area > 0.0f && b.area > 0.0f)) return 0.0f;
     // work relative to a's centre to keep fp32 cancellation small
     float ax[4], ay[4], bx[4], by[4];
 #pragma unroll
@@ -41,28 +48,20 @@ __global__ void __launch_bounds__(256) nms_bev_kernel(const float *boxes, const 
     const int g = blockIdx.x, tid = threadIdx.x;
     const int off = offsets[g], n = offsets[g + 1] - off;
     extern __shared__ __align__(16) unsigned char smem[];
-    int np2 = 1; while (np2 < n) np2 <<= 1;
+    const int np2 = mr_nms_padded(n);
     float *skey = (float *)smem;                         // [np2]
     int *sidx = (int *)(skey + np2);                     // [np2]
     NmsBox *sbox = (NmsBox *)(sidx + np2);               // [n] in sorted order
     const int nw = (n + 31) >> 5;
     unsigned *srow = (unsigned *)(sbox + n);             // [n][nw] suppression bits (j > i, IoU > thr)
     if (n <= 0) { if (tid == 0) num_keep[g] = 0; return; }
-    for (int i = tid; i < np2; i += 256) { skey[i] = (i < n) ? scores[off + i] : -__int_as_float(0x7f800000); sidx[i] = (i < n) ? i : 0x7fffffff; }
+    for (int i = tid; i < np2; i += 256) mr_nms_fill(skey, sidx, i, n, scores + off);
     __syncthreads();
-    // bitonic sort: descending score, ties by ascending index; NaN scores sort last
+    // bitonic sort into the order of nms_order.inc: descending score, ties by ascending index, NaN scores last, padding after them —
+    // so the first n places hold a permutation of 0 .. n-1 whatever the scores are
     for (int k = 2; k <= np2; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < np2; i += 256) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const float ki = skey[i], kl = skey[l]; const int ii = sidx[i], il = sidx[l];
-                    // "i before l" in the final order
-                    const bool i_first = (ki > kl) || (ki == kl && ii < il) || (kl != kl && ki == ki);
-                    const bool up = (i & k) == 0;
-                    if (up ? !i_first : i_first) { skey[i] = kl; skey[l] = ki; sidx[i] = il; sidx[l] = ii; }
-                }
-            }
+            for (int i = tid; i < np2; i += 256) mr_nms_step(skey, sidx, i, j, k);
             __syncthreads();
         }
     for (int i = tid; i < n; i += 256) {

@@ -34,7 +34,7 @@ c_ip = ctypes.POINTER(ctypes.c_int)
 
 def build(force=False):
     so = os.path.join(_HERE, 'libpnp_oracle.so')
-    srcs = [os.path.join(_HERE, f) for f in ('pnp_oracle.c', 'epnp.inc', 'jet.inc', 'Makefile')]
+    srcs = [os.path.join(_HERE, f) for f in ('pnp_oracle.c', 'epnp.inc', 'jet.inc', 'Makefile', '../monorun_amd/csrc/nms_order.inc')]
     if force or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in srcs):
         subprocess.check_call(['make', '-C', _HERE, '-B', 'libpnp_oracle.so'],
                               stdout=subprocess.DEVNULL)
@@ -649,26 +649,59 @@ def rotated_iou_bev(a, b):
         pa = pa[::-1]
     if _poly_area(pb) < 0:
         pb = pb[::-1]
-    inter = _clip(pa, pb)
-    ov = abs(_poly_area(inter)) if len(inter) >= 3 else 0.0
     sa = abs((a[2] - a[0]) * (a[3] - a[1]))
     sb = abs((b[2] - b[0]) * (b[3] - b[1]))
+    if sa == 0 or sb == 0:
+        return 0.0              # a segment or a point meets nothing in a set of positive area (and has no sides for the clipper to test)
+    inter = _clip(pa, pb)
+    ov = abs(_poly_area(inter)) if len(inter) >= 3 else 0.0
     return ov / max(sa + sb - ov, 1e-8)
 
 
+def nms_order_rule(scores):
+    """The order the NMS visits its boxes in, as a total order on (score, index): non-NaN scores before NaN scores; among non-NaN
+    scores descending (+inf first, -inf last); equal scores by ascending index; NaN scores among themselves by ascending index.
+    (torch.sort(descending=True) would put NaN first.)  Plain Python on purpose: independent of nms_order.inc / orc_nms_order."""
+    s = [float(v) for v in np.asarray(scores).reshape(-1)]
+    return sorted(range(len(s)), key=lambda i: (1, 0.0, i) if s[i] != s[i] else (0, -s[i], i))
+
+
+def nms_order(scores):
+    """The same order from the HIP kernel's own padded sorting network and comparator (csrc/nms_order.inc) run on the host: the first
+    n sorted places, which hold the index 0x7fffffff wherever the network lets a padding entry through."""
+    s = _f(np.asarray(scores).reshape(-1))
+    out = np.full(len(s), -1, np.int32)
+    f = lib().orc_nms_order
+    f.restype = ctypes.c_int
+    f(_p(s, c_fp), ctypes.c_int(len(s)), _p(out, c_ip))
+    return out
+
+
+def _bev_reach(b):
+    """centre and half-diagonal of each [x1, y1, x2, y2, ry] row: two boxes whose centres are further apart than the sum of their
+    half-diagonals cannot intersect"""
+    b = np.asarray(b, np.float64).reshape(-1, 5)
+    return 0.5 * (b[:, 0:2] + b[:, 2:4]), 0.5 * np.hypot(b[:, 2] - b[:, 0], b[:, 3] - b[:, 1])
+
+
 def nms_bev(boxes_xyxyr, scores, thr):
-    """Greedy rotated NMS; returns kept indices into the input, in descending-score order
-    (ties: lower index first)."""
+    """Greedy rotated NMS; returns kept indices into the input, in the order of nms_order_rule (descending score, ties: lower index
+    first, NaN scores last).  Pairs too far apart to intersect (IoU exactly 0) are not clipped."""
     boxes = np.asarray(boxes_xyxyr, np.float64)
     scores = np.asarray(scores, np.float64)
-    order = sorted(range(len(scores)), key=lambda i: (-scores[i], i))
+    order = nms_order_rule(scores)
+    ctr, rad = _bev_reach(boxes)
     keep, dead = [], set()
     for ii, i in enumerate(order):
         if i in dead:
             continue
         keep.append(i)
+        if thr < 0:
+            near = np.ones(len(boxes), bool)                      # IoU 0 > thr: every pair counts
+        else:
+            near = np.hypot(ctr[:, 0] - ctr[i, 0], ctr[:, 1] - ctr[i, 1]) <= (rad + rad[i]) * (1 + 1e-9) + 1e-9
         for j in order[ii + 1:]:
-            if j not in dead and rotated_iou_bev(boxes[i], boxes[j]) > thr:
+            if near[j] and j not in dead and rotated_iou_bev(boxes[i], boxes[j]) > thr:
                 dead.add(j)
     return np.array(keep, np.int64)
 

@@ -1187,3 +1187,24 @@ int orc_max_threads(void) {
     return 1;
 #endif
 }
+
+/* The visiting order of the rotated-BEV NMS (nms_bev_kernel): the kernel's own padded bitonic network and comparator, compiled from
+ * the one include both share and run here position by position, step by step.  out_index receives the first n sorted places (a
+ * permutation of 0 .. n-1 if the network is right; a padding index MR_NMS_PAD_INDEX would show here as it would in the kernel). */
+#define MR_NMS_FN static inline
+#include "../monorun_amd/csrc/nms_order.inc"
+#undef MR_NMS_FN
+int orc_nms_order(const float *scores, int n, int *out_index) {
+    if (n <= 0) return 0;
+    const int np2 = mr_nms_padded(n);
+    float *key = (float *)malloc(sizeof(float) * (size_t)np2);
+    int *idx = (int *)malloc(sizeof(int) * (size_t)np2);
+    if (!key || !idx) { free(key); free(idx); return -1; }
+    for (int i = 0; i < np2; ++i) mr_nms_fill(key, idx, i, n, scores);
+    for (int k = 2; k <= np2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1)
+            for (int i = 0; i < np2; ++i) mr_nms_step(key, idx, i, j, k);
+    memcpy(out_index, idx, sizeof(int) * (size_t)n);
+    free(key); free(idx);
+    return np2;
+}

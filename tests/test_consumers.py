@@ -58,26 +58,30 @@ def test_nms_oracle_properties(orc):
                                                  [(0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2), (3, 0), (3, 1), (3, 2), (3, 3)]], 1))
 
 
+NMS_ORACLE_SEED = 7        # seed 2 had a pair 6e-7 from the threshold 0.25
+
+
+def nms_oracle_groups(seed=None):
+    """the groups of test_gpu_nms_matches_oracle.  No pair of any of them has an fp64 IoU within 1e-4 of 0.01 or 0.25
+    (tests/test_nms_bev_cases_cpu.py asserts it for this seed), so fp32 and fp64 decide every pair alike."""
+    rng = np.random.default_rng(NMS_ORACLE_SEED if seed is None else seed)
+    groups = [_rand_boxes(rng, n, spread=sp) for n, sp in ((100, 25.0), (37, 6.0), (1, 1.0), (2, 0.5), (300, 40.0), (64, 3.0))]
+    groups.append(np.repeat(_rand_boxes(rng, 1), 5, 0))                          # identical boxes: only one survives
+    scores = [rng.uniform(0, 1, len(g)).astype(np.float32) for g in groups]
+    scores[-1][:] = 0.5                                                          # score ties -> lower index first
+    return groups, scores
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('thr', [0.01, 0.25])
 def test_gpu_nms_matches_oracle(orc, thr):
     from monorun_amd.consumers import nms_bev
     dev = torch.device('cuda:0')
-    rng = np.random.default_rng(2)
-    groups = [_rand_boxes(rng, n, spread=sp) for n, sp in ((100, 25.0), (37, 6.0), (1, 1.0), (2, 0.5), (300, 40.0), (64, 3.0))]
-    groups.append(np.repeat(_rand_boxes(rng, 1), 5, 0))                          # identical boxes: only one survives
-    scores = [rng.uniform(0, 1, len(g)).astype(np.float32) for g in groups]
-    scores[-1][:] = 0.5                                                          # score ties -> lower index first
+    groups, scores = nms_oracle_groups()
     out = nms_bev([torch.from_numpy(g).to(dev) for g in groups], [torch.from_numpy(s).to(dev) for s in scores], thr)
     torch.cuda.synchronize()
     for g, s, k in zip(groups, scores, out):
-        ref = orc.nms_bev(g, s, thr)
-        k = k.cpu().numpy()
-        if np.array_equal(k, ref):
-            continue
-        # a difference is only acceptable at an fp32-vs-fp64 knife edge: some pair's IoU within 1e-4 of thr
-        ious = [orc.rotated_iou_bev(g[i], g[j]) for i in range(len(g)) for j in range(i + 1, len(g))]
-        assert any(abs(v - thr) < 1e-4 for v in ious), (k, ref)
+        assert np.array_equal(k.cpu().numpy(), orc.nms_bev(g, s, thr))            # no knife edge in these groups: equality
     assert out[-1].cpu().tolist() == [0]
 
 
