@@ -16,7 +16,11 @@ Hot path: on CUDA fp32 within the caps (4096 RoIs per image, 16 classes) ``get_b
 HIP launches (rank, the NMS's two, select), no atomics, bitwise reproducible — and ``padded=True`` performs no host synchronisation.
 Everything else runs :func:`bbox_head_rank_torch`, :func:`monorun_amd.proposals.nms_grouped` and :func:`select_torch`: the same rule.
 
-Not provided: ``get_targets`` / ``loss`` (they need an assigner and a sampler), ``with_avg_pool``, other ``ConvFCBBoxHead`` shapes.
+Training: ``get_targets``, ``loss``, ``accuracy``, ``regress_by_class`` and ``refine_bboxes`` are mmdet's ``BBoxHead`` ones
+on the sampling results of :mod:`monorun_amd.assigners`, in torch; ``get_targets`` also takes a ``BatchSamplingResult`` and then, like
+``loss``, performs no host synchronisation.
+
+Not provided: ``with_avg_pool``, other ``ConvFCBBoxHead`` shapes.
 """
 import ctypes
 
@@ -27,6 +31,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import proposals as P
+from .assigners import BatchSamplingResult, _ascending, bbox2delta
+from .detection_losses import resolve
 from .losses import UnbuiltLoss, build_loss
 
 MAX_ROIS = 4096         # MR_BBOX_MAX_ROIS of include/monorun_bbox.h
@@ -368,3 +374,122 @@ class Shared2FCBBoxHead(nn.Module):
         if not many:
             return out[0]
         return [d for d, _ in out], [l for _, l in out]
+
+    # -------------------------------------------------------------------------------------------- training
+    def get_targets(self, sampling_results, gt_bboxes, gt_labels, rcnn_train_cfg, concat=True):
+        """mmdet's ``get_targets``: per image the positives, then the negatives -> (labels int64: ``num_classes`` on the negatives,
+        label_weights: ``pos_weight`` (1 when <= 0) on the positives and 1 on the negatives, bbox_targets: the coder's deltas of the
+        positives against their ground truths, bbox_weights: 1 on the positives), concatenated over the images unless ``concat=False``.
+        A :class:`monorun_amd.assigners.BatchSamplingResult` gives the padded form instead, without a host synchronisation: per image
+        ``num`` rows, the sampled boxes in ascending index order, then rows of weight 0 — (rois (N·num, 5), labels, label_weights,
+        bbox_targets, bbox_weights), whose first entry replaces ``bbox2roi``."""
+        pos_weight = float(_cfg_get(rcnn_train_cfg, 'pos_weight')) if _has(rcnn_train_cfg, 'pos_weight') else -1.0
+        pos_weight = 1.0 if pos_weight <= 0 else pos_weight
+        if isinstance(sampling_results, BatchSamplingResult):
+            return self._padded_targets(sampling_results, pos_weight)
+        out = []
+        for res in sampling_results:
+            pos, neg = res.pos_bboxes[:, :4], res.neg_bboxes
+            num_pos, num = pos.shape[0], pos.shape[0] + neg.shape[0]
+            labels = pos.new_full((num,), self.num_classes, dtype=torch.int64)
+            label_weights, bbox_targets, bbox_weights = pos.new_zeros(num), pos.new_zeros(num, 4), pos.new_zeros(num, 4)
+            if num_pos > 0:
+                labels[:num_pos] = res.pos_gt_labels
+                label_weights[:num_pos] = pos_weight
+                bbox_targets[:num_pos] = bbox2delta(pos, res.pos_gt_bboxes, self.target_means, self.target_stds)
+                bbox_weights[:num_pos] = 1
+            label_weights[num_pos:] = 1.0
+            out.append((labels, label_weights, bbox_targets, bbox_weights))
+        if not concat:
+            return tuple(list(t) for t in zip(*out))
+        return tuple(torch.cat(t, 0) for t in zip(*out))
+
+    def _padded_targets(self, s, pos_weight):
+        N, T = s.gt_inds.shape
+        num = s.pos_inds.shape[1]
+        rows = _ascending(s.pos_mask | s.neg_mask, num)                                             # (N, num), -1 past the count
+        live, at = rows >= 0, rows.clamp(min=0)
+        pos = s.pos_mask.gather(1, at) & live
+        boxes = s.bboxes.gather(1, at[..., None].expand(N, num, 4))
+        own = (s.gt_inds.gather(1, at) - 1).clamp(min=0)                                            # (N, num): each row's ground truth
+        Gm = max(max(s.num_gts, default=0), 1)
+        gts = torch.stack([torch.cat((g, g.new_zeros(Gm - g.shape[0], 4))) for g in s.gt_bboxes]).to(boxes.dtype)
+        mine = gts.gather(1, own.clamp(max=Gm - 1)[..., None].expand(N, num, 4))
+        unit = torch.stack([torch.full((), float(k >= 2), dtype=boxes.dtype, device=boxes.device) for k in range(4)])
+        safe = lambda b: torch.where(pos[..., None], b, unit)                                      # [0, 0, 1, 1] where no delta is wanted
+        w = pos.to(boxes.dtype)
+        deltas = bbox2delta(safe(boxes), safe(mine), self.target_means, self.target_stds) * w[..., None]
+        labels = torch.where(pos, s.labels.gather(1, at), self.num_classes)
+        image = torch.arange(N, device=boxes.device, dtype=boxes.dtype)[:, None, None].expand(N, num, 1)
+        rois = torch.cat((image, torch.where(live[..., None], boxes, unit)), dim=-1)
+        return (rois.reshape(-1, 5), labels.reshape(-1), (w * pos_weight + (live & ~pos).to(boxes.dtype)).reshape(-1), deltas.reshape(-1, 4),
+                w[..., None].expand(N, num, 4).reshape(-1, 4))
+
+    def loss(self, cls_score, bbox_pred, rois, labels, label_weights, bbox_targets, bbox_weights, reduction_override=None):
+        """mmdet's ``loss``: -> dict(loss_cls, acc, loss_bbox).  ``loss_cls`` with ``avg_factor = max(sum(label_weights > 0), 1)`` as a
+        tensor and ``acc`` over the rows of positive weight; the regression picks each positive's own class columns, is weighted by
+        ``bbox_weights`` and has as ``avg_factor`` the number of rows (of positive weight: the padded form's other rows are no samples).
+        With no positives it is 0 = ``bbox_pred[pos].sum()``.  No host synchronisation."""
+        losses = dict()
+        live = label_weights > 0
+        rows = live.sum().clamp(min=1).to(torch.float32)
+        if cls_score is not None:
+            losses['loss_cls'] = resolve(self.loss_cls)(cls_score, labels, label_weights, avg_factor=rows, reduction_override=reduction_override)
+            losses['acc'] = accuracy(cls_score, labels, weight=live)
+        if bbox_pred is not None:
+            R = bbox_pred.shape[0]
+            pos = (labels >= 0) & (labels < self.num_classes)
+            if self.reg_class_agnostic:
+                own = bbox_pred.reshape(R, 4)
+            else:
+                cls = torch.where(pos, labels, 0)
+                own = bbox_pred.reshape(R, -1, 4).gather(1, cls[:, None, None].expand(R, 1, 4)).reshape(R, 4)
+            weight = bbox_weights * pos[:, None].to(bbox_weights.dtype)
+            losses['loss_bbox'] = resolve(self.loss_bbox)(own, bbox_targets, weight, avg_factor=rows, reduction_override=reduction_override)
+        return losses
+
+    def regress_by_class(self, rois, label, bbox_pred, img_meta):
+        """mmdet's ``regress_by_class``: rois (n, 4) or (n, 5), label (n,), bbox_pred (n, 4C) or (n, 4) -> the rois moved by their class's
+        deltas and clamped to ``img_meta['img_shape']``."""
+        assert rois.shape[1] in (4, 5), 'regress_by_class: rois (n, 4) or (n, 5)'
+        if not self.reg_class_agnostic:
+            bbox_pred = bbox_pred.reshape(bbox_pred.shape[0], -1, 4).gather(1, label[:, None, None].expand(-1, 1, 4).long()).reshape(-1, 4)
+        rois5 = rois if rois.shape[1] == 5 else torch.cat((rois.new_zeros(rois.shape[0], 1), rois), dim=1)
+        hw = rois.new_tensor([float(img_meta['img_shape'][0]), float(img_meta['img_shape'][1])]).expand(rois.shape[0], 2)
+        boxes = decode_torch(rois5, bbox_pred, hw, None, self.target_means, self.target_stds)[:, 0].to(rois.dtype)
+        return boxes if rois.shape[1] == 4 else torch.cat((rois[:, :1], boxes), dim=1)
+
+    def refine_bboxes(self, rois, labels, bbox_preds, pos_is_gts, img_metas):
+        """mmdet's ``refine_bboxes``: per image the rois regressed by their labels' deltas, without the positives that are ground truths."""
+        img_ids = rois[:, 0].long().unique(sorted=True)
+        assert img_ids.numel() <= len(img_metas)
+        out = []
+        for i in range(len(img_metas)):
+            inds = torch.nonzero(rois[:, 0] == i, as_tuple=False).squeeze(dim=1)
+            bboxes = self.regress_by_class(rois[inds, 1:], labels[inds], bbox_preds[inds], img_metas[i])
+            keep = pos_is_gts[i].new_ones(inds.numel())
+            keep[:len(pos_is_gts[i])] = 1 - pos_is_gts[i]
+            out.append(bboxes[keep.bool()])
+        return out
+
+
+def _has(cfg, key):
+    return key in cfg if isinstance(cfg, dict) else hasattr(cfg, key)
+
+
+def accuracy(pred, target, topk=1, thresh=None, weight=None):
+    """mmdet's ``accuracy``: the percentage of rows whose ``topk`` highest scores hold the target (above ``thresh``, if given), a tensor
+    (1,) — a tuple of them for a tuple of ``topk``.  ``weight`` (R,) bool: the rows that count (default: all)."""
+    ks = (topk,) if isinstance(topk, int) else tuple(topk)
+    rows = pred.shape[0] if weight is None else weight.sum().clamp(min=1)
+    if pred.shape[0] == 0:
+        res = [pred.new_zeros(1) for _ in ks]
+        return res[0] if isinstance(topk, int) else tuple(res)
+    value, label = pred.topk(max(ks), dim=1)
+    correct = label.t() == target[None, :]
+    if thresh is not None:
+        correct = correct & (value > thresh).t()
+    if weight is not None:
+        correct = correct & weight[None, :]
+    res = [correct[:k].reshape(-1).float().sum(0, keepdim=True) * (100.0 / rows) for k in ks]
+    return res[0] if isinstance(topk, int) else tuple(res)

@@ -25,6 +25,7 @@
 #include "monorun_roi.h"
 #include "monorun_proposals.h"
 #include "monorun_bbox.h"
+#include "monorun_assign.h"
 
 namespace {
 
@@ -112,6 +113,7 @@ constexpr size_t kNocLds = sizeof(double) * (2 * 4 * kRedN + 2 * 40);     // red
 #include "roi_extract_kernel.inc"
 #include "proposals_kernel.inc"
 #include "bbox_head_kernel.inc"
+#include "assign_kernel.inc"
 #include "consumers_kernel.inc"
 #include "host_launch.inc"
 
@@ -136,6 +138,7 @@ extern "C" {
 #include "roi_extract_abi.inc"
 #include "proposals_abi.inc"
 #include "bbox_head_abi.inc"
+#include "assign_abi.inc"
 #include "debug_abi.inc"
 
 }  // extern "C"

@@ -10,13 +10,22 @@ convolutions and the sorts are torch; decode and NMS are three HIP launches for 
 ``(N, nms_post, 5)`` with NaN rows past ``counts`` (N,) int32 and performs no host synchronisation; the list form is the padded form plus
 one read of ``counts``.
 
-Training targets and the RPN's ``loss`` (anchor assignment, sampling, the two losses) are not provided: they are torch ops.
+Training: ``get_anchors``, ``get_targets``, ``loss`` and ``forward_train`` are mmdet's ``AnchorHead`` ones on
+:mod:`monorun_amd.assigners` — ONE ``assign_batch`` (two HIP launches for all images and levels, the shared anchors are not copied) and one
+``sample_batch`` per step; the regression targets are the launch's deltas times the sampled-positive mask.  ``loss`` and ``forward_train``
+(with ``padded=True`` in ``proposal_cfg``) perform no host synchronisation.
 """
+import math
+
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import proposals as P
+from .assigners import build_assigner, build_sampler
+from .detection_losses import resolve
+from .losses import build_loss
 
 
 class AnchorGenerator:
@@ -44,6 +53,16 @@ class AnchorGenerator:
     def num_base_anchors(self):
         return [b.shape[0] for b in self.base_anchors]
 
+    def valid_flags(self, featmap_sizes, pad_shape):
+        """mmdet's ``valid_flags`` of one image as a host array (sum H·W·A,) bool: the cells inside ``pad_shape`` (h, w[, c]), each
+        repeated for its A anchors."""
+        out = []
+        for (h, w), s, base in zip(featmap_sizes, self.strides, self.base_anchors):
+            valid_h, valid_w = min(int(math.ceil(pad_shape[0] / s)), h), min(int(math.ceil(pad_shape[1] / s)), w)
+            cell = (np.arange(h) < valid_h)[:, None] & (np.arange(w) < valid_w)[None, :]
+            out.append(np.repeat(cell.reshape(-1), base.shape[0]))
+        return np.concatenate(out)
+
     def grid_anchors(self, featmap_sizes, device='cpu'):
         """mmdet's ``grid_anchors``: per level (H·W·A, 4), anchor ``(y·W + x)·A + a`` = base[a] + (x·s, y·s, x·s, y·s)."""
         out = []
@@ -54,6 +73,13 @@ class AnchorGenerator:
             shifts = torch.stack((xx, yy, xx, yy), dim=-1)
             out.append((shifts[:, None, :] + base[None, :, :]).reshape(-1, 4).to(device))
         return out
+
+
+def _cfg(cfg, key, *default):
+    """An entry of a train / test config given as a dict or as an attribute object."""
+    if isinstance(cfg, dict):
+        return cfg.get(key, *default) if default else cfg[key]
+    return getattr(cfg, key, *default)
 
 
 def _image_shapes(img_metas, device):
@@ -71,7 +97,8 @@ class RPNHeadMod(nn.Module):
     def __init__(self, in_channels, starting_level=0, feat_channels=256,
                  anchor_generator=dict(type='AnchorGenerator', scales=[8], ratios=[0.5, 1.0, 2.0], strides=[4, 8, 16, 32, 64]),
                  bbox_coder=dict(type='DeltaXYWHBBoxCoder', target_means=(.0, .0, .0, .0), target_stds=(1.0, 1.0, 1.0, 1.0)),
-                 test_cfg=None, train_cfg=None, **kwargs):
+                 loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0),
+                 loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0), test_cfg=None, train_cfg=None, **kwargs):
         super().__init__()
         coder = dict(bbox_coder)
         assert coder.pop('type', 'DeltaXYWHBBoxCoder') == 'DeltaXYWHBBoxCoder', 'bbox_coder: DeltaXYWHBBoxCoder only'
@@ -80,6 +107,13 @@ class RPNHeadMod(nn.Module):
         self.target_means = tuple(float(m) for m in coder.get('target_means', (0.0,) * 4))
         self.target_stds = tuple(float(s) for s in coder.get('target_stds', (1.0,) * 4))
         self.test_cfg, self.train_cfg = test_cfg, train_cfg
+        self.loss_cls, self.loss_bbox = build_loss(loss_cls), build_loss(loss_bbox)      # an UnbuiltLoss without mmdet: `loss` resolves it
+        self.assigner = self.sampler = None
+        if train_cfg is not None and _cfg(train_cfg, 'assigner', None) is not None:
+            self.assigner = build_assigner(_cfg(train_cfg, 'assigner'))
+            self.sampler = build_sampler(_cfg(train_cfg, 'sampler', dict(type='RandomSampler', num=256, pos_fraction=0.5,
+                                                                           add_gt_as_proposals=False)), context=self)
+        self._anchor_cache = {}
         self.num_anchors = self.anchor_generator.num_base_anchors[0]
         self.rpn_conv = nn.Conv2d(in_channels, feat_channels, 3, padding=1)
         self.rpn_cls = nn.Conv2d(feat_channels, self.num_anchors, 1)
@@ -132,6 +166,79 @@ class RPNHeadMod(nn.Module):
         if padded:
             return out, num
         return [out[n, :k] for n, k in enumerate(num.tolist())]
+
+    # -------------------------------------------------------------------------------------------- training
+    def get_anchors(self, featmap_sizes, img_metas, device='cuda'):
+        """mmdet's ``get_anchors``, dense: (anchors of every level, one set for all images: a list of (H·W·A, 4); valid (N, sum H·W·A)
+        bool from each image's ``pad_shape``).  The anchors are cached per sizes and device; no blocking copy."""
+        sizes = tuple((int(h), int(w)) for h, w in featmap_sizes)
+        key = (sizes, str(device))
+        if key not in self._anchor_cache:
+            self._anchor_cache[key] = self.anchor_generator.grid_anchors(sizes, device)
+        flags = np.stack([self.anchor_generator.valid_flags(sizes, m['pad_shape']) for m in img_metas])
+        return self._anchor_cache[key], P.host_to_device(flags.tolist(), torch.bool, device)
+
+    def get_targets(self, anchor_list, valid_flags, gt_bboxes, img_metas, gt_bboxes_ignore=None, generator=None, keys=None):
+        """mmdet's ``AnchorHead.get_targets`` for all images at once: ``allowed_border``, one ``assign_batch``, one ``sample_batch``.
+        anchor_list, valid_flags: :meth:`get_anchors`' results.  -> (labels (N, B) int64: 0 on the sampled positives, 1 elsewhere;
+        label_weights (N, B): ``pos_weight`` (1 when <= 0) on the sampled positives, 1 on the sampled negatives; bbox_targets (N, B, 4):
+        the launch's deltas on the sampled positives; bbox_weights (N, B, 4): 1 there; num_total_pos, num_total_neg: device scalars,
+        the sum over the images of max(count, 1)).  B runs over the levels in order.  No host synchronisation."""
+        if self.assigner is None:
+            raise RuntimeError('RPNHeadMod.get_targets: the head was built without a train_cfg')
+        if self.sampler.add_gt_as_proposals:
+            raise NotImplementedError('RPNHeadMod: a sampler with add_gt_as_proposals=True is not provided (anchors have no row for them)')
+        anchors = torch.cat(list(anchor_list)) if not isinstance(anchor_list, torch.Tensor) else anchor_list
+        border = _cfg(self.train_cfg, 'allowed_border', -1)
+        present = valid_flags
+        if border >= 0:
+            shape = _image_shapes(img_metas, anchors.device)                     # (N, 2) img_h, img_w
+            inside = ((anchors[None, :, 0] >= -border) & (anchors[None, :, 1] >= -border)
+                      & (anchors[None, :, 2] < shape[:, 1:2] + border) & (anchors[None, :, 3] < shape[:, 0:1] + border))
+            present = present & inside
+        result = self.assigner.assign_batch(anchors, gt_bboxes, gt_bboxes_ignore, None, valid=present, means=self.target_means,
+                                            stds=self.target_stds)
+        sampled = self.sampler.sample_batch(result, anchors, gt_bboxes, generator=generator, keys=keys)
+        pos, neg = sampled.pos_mask, sampled.neg_mask
+        pos_weight = float(_cfg(self.train_cfg, 'pos_weight', -1))
+        labels = torch.where(pos, 0, 1)
+        label_weights = pos.to(torch.float32) * (1.0 if pos_weight <= 0 else pos_weight) + neg.to(torch.float32)
+        bbox_weights = pos[..., None].to(torch.float32).expand(-1, -1, 4)
+        return (labels, label_weights, result.deltas * bbox_weights, bbox_weights, sampled.num_pos.clamp(min=1).sum(),
+                sampled.num_neg.clamp(min=1).sum())
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore=None, generator=None, keys=None):
+        """mmdet's ``RPNHead.loss``: -> dict(loss_rpn_cls=[per level], loss_rpn_bbox=[per level]).  Per level the NHWC-flattened outputs,
+        the sigmoid cross entropy against ``label == 0`` and the regression loss on the deltas, both with
+        ``avg_factor = num_total_pos + num_total_neg``.  No host synchronisation."""
+        sizes = [tuple(c.shape[-2:]) for c in cls_scores]
+        N, dev = cls_scores[0].shape[0], cls_scores[0].device
+        anchors, flags = self.get_anchors(sizes, img_metas, dev)
+        labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg = self.get_targets(
+            anchors, flags, gt_bboxes, img_metas, gt_bboxes_ignore, generator=generator, keys=keys)
+        avg = (num_pos + num_neg).to(torch.float32)
+        loss_cls, loss_bbox = resolve(self.loss_cls), resolve(self.loss_bbox)
+        out_cls, out_bbox, first = [], [], 0
+        for c, r, a in zip(cls_scores, bbox_preds, anchors):
+            sl = slice(first, first + a.shape[0])
+            first += a.shape[0]
+            score = c.permute(0, 2, 3, 1).reshape(-1, 1)
+            out_cls.append(loss_cls(score, (labels[:, sl] == 0).reshape(-1, 1), label_weights[:, sl].reshape(-1, 1), avg_factor=avg))
+            out_bbox.append(loss_bbox(r.permute(0, 2, 3, 1).reshape(-1, 4), bbox_targets[:, sl].reshape(-1, 4),
+                                      bbox_weights[:, sl].reshape(-1, 4), avg_factor=avg))
+        return dict(loss_rpn_cls=out_cls, loss_rpn_bbox=out_bbox)
+
+    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
+        """mmdet's ``forward_train``: the head on the maps ``x``, :meth:`loss`, and with a ``proposal_cfg`` the proposals of
+        :meth:`get_bboxes` -> (losses, proposal_list); with ``padded=True`` in ``proposal_cfg`` the proposals are get_bboxes' padded pair
+        and nothing synchronises.  ``gt_labels`` is accepted and, as in mmdet's RPN, unused."""
+        outs = self(x)
+        losses = self.loss(*outs, gt_bboxes, img_metas, gt_bboxes_ignore, **kwargs)
+        if proposal_cfg is None:
+            return losses
+        cfg = dict(proposal_cfg)
+        padded = bool(cfg.pop('padded', False))
+        return losses, self.get_bboxes(*outs, img_metas, cfg=cfg, padded=padded)
 
     def simple_test_rpn(self, x, img_metas, padded=False):
         """mmdet's ``RPNTestMixin.simple_test_rpn``: the head on the maps ``x``, then :meth:`get_bboxes` with ``test_cfg``."""
