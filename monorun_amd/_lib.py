@@ -51,6 +51,7 @@ LATER_HEADERS = {
     'proposals': ('monorun_proposals.h', ('mr_proposal_decode', 'mr_nms_workspace_bytes', 'mr_nms_grouped')),        # section 19
     'bbox': ('monorun_bbox.h', ('mr_bbox_head_rank', 'mr_bbox_head_select', 'mr_bbox_head_workspace_bytes', 'mr_bbox_head_detect')),   # section 20
     'assign': ('monorun_assign.h', ('mr_assign_workspace_bytes', 'mr_assign_max_iou')),                               # section 21
+    'fpn': ('monorun_fpn.h', ('mr_fpn_topdown_forward', 'mr_fpn_topdown_backward')),                                   # section 22
 }
 
 

@@ -26,6 +26,7 @@
 #include "monorun_proposals.h"
 #include "monorun_bbox.h"
 #include "monorun_assign.h"
+#include "monorun_fpn.h"
 
 namespace {
 
@@ -114,6 +115,7 @@ constexpr size_t kNocLds = sizeof(double) * (2 * 4 * kRedN + 2 * 40);     // red
 #include "proposals_kernel.inc"
 #include "bbox_head_kernel.inc"
 #include "assign_kernel.inc"
+#include "fpn_kernel.inc"
 #include "consumers_kernel.inc"
 #include "host_launch.inc"
 
@@ -139,6 +141,7 @@ extern "C" {
 #include "proposals_abi.inc"
 #include "bbox_head_abi.inc"
 #include "assign_abi.inc"
+#include "fpn_abi.inc"
 #include "debug_abi.inc"
 
 }  // extern "C"
