@@ -52,6 +52,8 @@ LATER_HEADERS = {
     'bbox': ('monorun_bbox.h', ('mr_bbox_head_rank', 'mr_bbox_head_select', 'mr_bbox_head_workspace_bytes', 'mr_bbox_head_detect')),   # section 20
     'assign': ('monorun_assign.h', ('mr_assign_workspace_bytes', 'mr_assign_max_iou')),                               # section 21
     'fpn': ('monorun_fpn.h', ('mr_fpn_topdown_forward', 'mr_fpn_topdown_backward')),                                   # section 22
+    'backbone': ('monorun_backbone.h', ('mr_bn_act_forward', 'mr_bn_act_backward_workspace_bytes', 'mr_bn_act_backward',
+                                        'mr_bn_relu_maxpool_forward')),                                                 # section 23
 }
 
 

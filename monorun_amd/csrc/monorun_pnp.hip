@@ -27,6 +27,7 @@
 #include "monorun_bbox.h"
 #include "monorun_assign.h"
 #include "monorun_fpn.h"
+#include "monorun_backbone.h"
 
 namespace {
 
@@ -116,6 +117,7 @@ constexpr size_t kNocLds = sizeof(double) * (2 * 4 * kRedN + 2 * 40);     // red
 #include "bbox_head_kernel.inc"
 #include "assign_kernel.inc"
 #include "fpn_kernel.inc"
+#include "backbone_kernel.inc"
 #include "consumers_kernel.inc"
 #include "host_launch.inc"
 
@@ -142,6 +144,7 @@ extern "C" {
 #include "bbox_head_abi.inc"
 #include "assign_abi.inc"
 #include "fpn_abi.inc"
+#include "backbone_abi.inc"
 #include "debug_abi.inc"
 
 }  // extern "C"
