@@ -169,7 +169,13 @@
             list = slist2;
             __syncthreads();
         }
-    } else __syncthreads();
+    } else {
+        // no loop: the list is the candidate list, and its mask (the bit row below) is built here from it — every thread sets the bits of the entries it loaded
+        for (int i = tid; i < (P + 31) >> 5; i += NT) smask[i] = 0u;
+        __syncthreads();
+        for (int i = tid; i < n; i += NT) { const int pidx = slist[i]; atomicOr(&smask[pidx >> 5], 1u << (pidx & 31)); }
+        __syncthreads();
+    }
     EPC_STAMP(4);
 
     if (ok) {
@@ -221,6 +227,13 @@
             if (mode == EP_MODE_RANSAC)
                 for (int p = t; p < P; p += NT - 64) cv.init_mask[(long long)b * P + p] = (uint8_t)((smask[p >> 5] >> (p & 31)) & 1u);
             for (int i = t; i < nn; i += NT - 64) ea.w.fit[(long long)b * ea.w.pstride + i] = list[i];
+            // ... and the list once more as a mask, one bit per point: what the LM launch that carries the re-fit keeps in LDS beside the list
+            // (it used to rebuild both from init_mask's bytes)
+            const int nw32 = (P + 31) >> 5;
+            const int nw64 = ep_fitbits_stride(P);
+            unsigned long long *const bits = ep_fitbits(ea.w, a.B) + (long long)b * nw64;
+            for (int c = t; c < nw64; c += NT - 64)
+                bits[c] = (unsigned long long)smask[2 * c] | ((unsigned long long)(2 * c + 1 < nw32 ? smask[2 * c + 1] : 0u) << 32);
         }
         __syncthreads();
         EPC_STAMP(5);

@@ -22,7 +22,7 @@
 // still wants iterations (the adaptive bound of RANSACUpdateNumIters drops to a handful after the first good model; the loop's state
 // parks in the workspace between the rounds).  Where the split falls changes the work, never the result.
 // Seven launches (round 3: thirteen); six for launch sets of fewer than 2048 objects, whose second round is ONE launch (epnp_round2_kernel).  Between the launches: a workspace laid out element-major ([element][problem]: a wave's accesses
-// to one element of consecutive problems are contiguous), 11.9 MB per 1024 objects since round 8 (round 5: 11.8 MB, round 4: 17 MB, round 3: 65 MB — the hypotheses' M^T M, control
+// to one element of consecutive problems are contiguous), 12.0 MB per 1024 objects since round 15 (the re-fit's list as a bit row, 104 B per object at P = 784; round 8: 11.9 MB, round 5: 11.8 MB, round 4: 17 MB, round 3: 65 MB — the hypotheses' M^T M, control
 // points, coordinates and eigenvectors no longer leave the registers).
 
 constexpr int kEpMeta = 12;           // ints per object in the workspace
@@ -86,15 +86,24 @@ size_t epnp_work_bytes(int B, int P, EpnpWork *w, unsigned char *base) {
     const size_t o_meta = take(sizeof(int) * kEpMeta * B), o_samp = take(sizeof(float) * kEpSampRec * nq), o_hrt = take(sizeof(double) * 12 * nq),
                  o_cand = take(sizeof(uint16_t) * ps * B), o_fit = take(sizeof(uint16_t) * ps * B), o_prep_r = take(sizeof(double) * 24 * B),
                  o_mtm_r = take(sizeof(double) * 144 * B), o_cand_r = take(sizeof(double) * kEpCandStride * B), o_cam = take(sizeof(float) * 4 * B), o_abt_r = take(sizeof(double) * 24 * B),
-                 o_spt = take(sizeof(uint16_t) * 5 * kEpMaxIters * B);
+                 o_spt = take(sizeof(uint16_t) * 5 * kEpMaxIters * B), o_bits = take(sizeof(unsigned long long) * ((size_t)(P + 63) >> 6) * B);
     if (w) {
         w->meta = (int *)(base + o_meta); w->samp = (float *)(base + o_samp); w->hrt = (double *)(base + o_hrt); w->cand = (uint16_t *)(base + o_cand);
         w->fit = (uint16_t *)(base + o_fit); w->prep_r = (double *)(base + o_prep_r); w->mtm_r = (double *)(base + o_mtm_r); w->cand_r = (double *)(base + o_cand_r); w->cam = (float *)(base + o_cam); w->abt_r = (double *)(base + o_abt_r);
         w->spt = (uint16_t *)(base + o_spt);
         w->nq = (long long)nq; w->pstride = (int)ps;
+        (void)o_bits;                                     // the bit rows follow spt: ep_fitbits()
     }
     return off;
 }
+
+// The re-fit's point list once more as a MASK, one bit per point (bit p & 63 of word p >> 6; (P + 63) / 64 words per object, on 8-byte boundaries), for the
+// LM launch that carries the re-fit: the last array of the workspace, behind spt (epnp_work_bytes' o_bits).  Located from spt rather than through a
+// pointer of its own in EpnpWork: that struct is part of every stage's kernel arguments, and the stages that do not touch the rows keep their code.
+__host__ __device__ __forceinline__ unsigned long long *ep_fitbits(const EpnpWork &w, const long long B) {
+    return (unsigned long long *)((unsigned char *)w.spt + (((size_t)sizeof(uint16_t) * 5 * kEpMaxIters * (size_t)B + 255) & ~(size_t)255));
+}
+__host__ __device__ __forceinline__ int ep_fitbits_stride(const int P) { return (P + 63) >> 6; }
 
 // the tensors of the call object b belongs to, as load_records and the camera read them
 struct EpCallView {
@@ -1142,7 +1151,7 @@ __device__ __forceinline__ void ep_store_init(uint8_t *init_ok, double *init_pos
 // Lane 0 leaves error, yaw and t of each candidate in scand[5 c ..].
 template <int NC, typename T, typename TL>
 __device__ __forceinline__ void ep_refit_errors(const EpRefitPoint<T, TL> &point, const EpCam &camu, const double *rec, const int c0, const int step,
-                                                const int nn, const double dn, const int lane, double *scand) {
+                                                const int nn, const double dn, const int lane, double *scand, unsigned long long *dbg_st = nullptr) {
     MR_EXACT
     double R[NC][9], t[NC][3], s[NC][1];
 #pragma unroll
@@ -1154,6 +1163,9 @@ __device__ __forceinline__ void ep_refit_errors(const EpRefitPoint<T, TL> &point
         for (int i = 0; i < 3; ++i) t[k][i] = r[9 + i];
         s[k][0] = 0.0;
     }
+#ifdef MR_DEBUG_STAMPS          // development builds (tools/gpu_lm_handover_stamps.py): the prologue's inputs — prep_r, the candidates' records — have arrived
+    if (dbg_st) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); if (threadIdx.x == 0) dbg_st[10] = __builtin_readcyclecounter(); }
+#endif
     for (int i = lane; i < nn; i += 64) {
         double pw[3], al[4], uu[2];
         point(i, pw, al, uu);
@@ -1183,27 +1195,29 @@ __device__ __forceinline__ void ep_refit_errors(const EpRefitPoint<T, TL> &point
 // that is, so both give the same bits.  (Up to round 7 the candidates' absolute orientation and the best one's Rodrigues vector ran here, on
 // three lanes of wave 0 while the other waves waited at a barrier.)
 //   scand: [3][5] doubles of LDS (error, yaw, t of the candidates).
+//   prep: the object's 24 doubles of prep_r (centroid, inverse basis), rec: its candidate records (cand_r) — in the workspace (epnp_refit_kernel) or where the
+//   caller parked them in LDS (the LM launch loads them with its tile); the same values, the same arithmetic.
 template <typename T, int NW, typename TL>
-__device__ __forceinline__ bool ep_refit_object(const TL &tl, const uint16_t *slist, const int nn, double *scand, const EpCam &cam, const EpnpWork &w,
-                                                const long long B, const int b, const bool norm_f64, const int wid, const int lane, double (&pose)[4]) {
+__device__ __forceinline__ bool ep_refit_object(const TL &tl, const uint16_t *slist, const int nn, double *scand, const EpCam &cam, const double *prep,
+                                                const double *rec, const bool norm_f64, const int wid, const int lane, double (&pose)[4],
+                                                unsigned long long *dbg_st = nullptr) {
     MR_EXACT
     double cws[4][3], ci[9];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) { cws[0][j] = uni(w.prep_r[(long long)b * 24 + j]); cws[1][j] = cws[2][j] = cws[3][j] = 0.0; }     // only the centroid is needed here
+    for (int j = 0; j < 3; ++j) { cws[0][j] = uni(prep[j]); cws[1][j] = cws[2][j] = cws[3][j] = 0.0; }     // only the centroid is needed here
 #pragma unroll
-    for (int i = 0; i < 9; ++i) ci[i] = uni(w.prep_r[(long long)b * 24 + (12 + i)]);
+    for (int i = 0; i < 9; ++i) ci[i] = uni(prep[12 + i]);
     const double dn = (double)nn;
     EpCam camu;
     camu.fx = uni(cam.fx); camu.fy = uni(cam.fy); camu.cx = uni(cam.cx); camu.cy = uni(cam.cy);
     const EpRefitPoint<T, TL> point{ tl, slist, camu, cws, ci, uni(1.0 / cam.fx), uni(1.0 / cam.fy), norm_f64 };
-    const double *rec = w.cand_r + (long long)b * kEpCandStride;
     if constexpr (NW >= 3) {                              // one candidate per wave (waves 3.. idle)
-        if (wid < 3) ep_refit_errors<1, T>(point, camu, rec, wid, NW, nn, dn, lane, scand);
+        if (wid < 3) ep_refit_errors<1, T>(point, camu, rec, wid, NW, nn, dn, lane, scand, dbg_st);
     } else if constexpr (NW == 2) {                       // wave 0: candidates 0 and 2, wave 1: candidate 1
-        if (wid == 0) ep_refit_errors<2, T>(point, camu, rec, 0, 2, nn, dn, lane, scand);
+        if (wid == 0) ep_refit_errors<2, T>(point, camu, rec, 0, 2, nn, dn, lane, scand, dbg_st);
         else ep_refit_errors<1, T>(point, camu, rec, 1, 2, nn, dn, lane, scand);
     } else {
-        ep_refit_errors<3, T>(point, camu, rec, 0, 1, nn, dn, lane, scand);
+        ep_refit_errors<3, T>(point, camu, rec, 0, 1, nn, dn, lane, scand, dbg_st);
     }
     __syncthreads();
     int N = 0;
@@ -1238,7 +1252,7 @@ __global__ void __launch_bounds__(kEpPoseThreads, MR_EP_REFIT_WAVES) epnp_refit_
         for (int i = tid; i < nn; i += NT) slist[i] = ea.w.fit[(long long)b * ea.w.pstride + i];
         const EpCam cam = ep_cam_of(cv, b);
         __syncthreads();
-        ok = ep_refit_object<T, NT / 64>(tl, slist, nn, scand, cam, ea.w, a.B, b, (meta[EP_M_REFIT] & 2) != 0, wid, lane, pose);
+        ok = ep_refit_object<T, NT / 64>(tl, slist, nn, scand, cam, ea.w.prep_r + (long long)b * 24, ea.w.cand_r + (long long)b * kEpCandStride, (meta[EP_M_REFIT] & 2) != 0, wid, lane, pose);
     }
     if (tid == 0) ep_store_init(cv.init_ok, cv.init_pose, cv.diag, b, ok, pose, meta);
 }

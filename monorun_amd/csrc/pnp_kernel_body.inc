@@ -58,6 +58,34 @@
     ld_k_vec<2>(a.ur, a.r_f64, ro, urv);
     ld_k_vec<2>(a.vr, a.r_f64, ro, vrv);
     const float thr_given = (a.ransac_thr && !a.from_head) ? a.ransac_thr[b] : 0.0f;
+#ifdef MR_K1_REFIT
+    // pnp_uncert_refit_kernel: what the consensus launch hands over — the re-fit's list (ascending point indices: stage 1's candidate list as it stands), the same
+    // set as a bit row, the list's length, the re-fit's inputs (prep_r: centroid and inverse basis; cand_r: the three candidates' records) — is loaded HERE, in the
+    // tile's round trip, and parked in LDS before the first barrier: stage 1 neither reads init_mask's bytes back nor ballots and scans them, and the re-fit
+    // prologue starts on values that have arrived.  Nothing below depends on another load: the row lengths come from P, not from meta.
+    // (The fp64, eight-wave instantiation keeps the byte path and the prologue's own loads: with the hand-over its register allocation went one 8-register granule
+    //  over the bound of tests/test_refit_kernel_resources.py.  More than two pairs of list entries per thread do the same to the fp32 two-wave one: the rest loads late.)
+    constexpr bool RF_LIST = !(std::is_same<T, double>::value && WPO == 8);
+    const int *const rf_meta = MR_K1_REFIT.w.meta + (long long)b * kEpMeta;
+    const int rf_nfit = rf_meta[EP_M_NFIT], rf_flag = rf_meta[EP_M_REFIT];
+    constexpr int kRfPre = RF_LIST ? 2 : 0;             // pairs of list entries a thread holds across the tile loop
+    const uint32_t *const rf_fit2 = (const uint32_t *)(MR_K1_REFIT.w.fit + (long long)b * MR_K1_REFIT.w.pstride);      // rows of pstride = P rounded up to 8 entries
+    const int rf_np2 = (P + 1) >> 1;
+    uint32_t rf_pre[kRfPre + 1];
+#pragma unroll
+    for (int k = 0; k < kRfPre; ++k) rf_pre[k] = (tid + k * NT < rf_np2) ? rf_fit2[tid + k * NT] : 0u;
+    const unsigned long long *const rf_bits = ep_fitbits(MR_K1_REFIT.w, MR_K1_REFIT.B) + (long long)b * nchunk;
+    unsigned long long rf_word = 0ull;
+    double rf_in = 0.0;
+    if constexpr (RF_LIST) {
+        rf_word = (tid < nchunk) ? rf_bits[tid] : 0ull;
+        // prep_r[0..23] | cand_r[0..39] of the object: one double per thread of wave 0
+        rf_in = (tid < 24) ? MR_K1_REFIT.w.prep_r[(long long)b * 24 + tid]
+              : (tid < 64) ? MR_K1_REFIT.w.cand_r[(long long)b * kEpCandStride + (tid - 24)] : 0.0;
+    }
+    static_assert(24 + kEpCandStride == 64 && sizeof(double) * 64 <= sizeof(float) * kHyp * 8, "the re-fit's inputs park in the K0 hypotheses' LDS, which this launch does not use");
+    double *const srf = (double *)shyp;                 // [24] prep_r | [40] cand_r
+#endif
     // ---------------------------------------------------------------- stage 0: inputs -> point records in LDS
     float head_thr = 0.0f;
     bool from_head = false;
@@ -130,6 +158,23 @@
         const unsigned *lsw = (const unsigned *)MR_K1_KARGS.plan.level_start;
         pl_ls0 = lsw[0]; pl_ls1 = lsw[1];
     }
+#ifdef MR_K1_REFIT
+    // the hand-over into LDS, behind the tile: list entries (pairs; the odd one past an odd P lands in the list's padding), the bit row (ONE_LIST: the mask
+    // itself; otherwise parked in sball and expanded to bytes below), the re-fit's inputs.  An object without a re-fit record (rf_flag == 0) has none of
+    // this — what lands here is then whatever the workspace held, and the byte path below overwrites all of it.
+    if constexpr (RF_LIST) {
+#pragma unroll
+        for (int k = 0; k < kRfPre; ++k) {
+            const int i = tid + k * NT;
+            if (i < rf_np2) { slist[2 * i] = (uint16_t)(rf_pre[k] & 0xffffu); slist[2 * i + 1] = (uint16_t)(rf_pre[k] >> 16); }
+        }
+        for (int i = tid + kRfPre * NT; i < rf_np2; i += NT) { const uint32_t v = rf_fit2[i]; slist[2 * i] = (uint16_t)(v & 0xffffu); slist[2 * i + 1] = (uint16_t)(v >> 16); }
+        unsigned long long *const wdst = ONE_LIST ? sbits : sball;
+        if (tid < nchunk) wdst[tid] = rf_word;
+        for (int c = tid + NT; c < nchunk; c += NT) wdst[c] = rf_bits[c];
+        if (tid < 64) srf[tid] = rf_in;
+    }
+#endif
     __syncthreads();
     MR_STAMP(1);
 
@@ -137,6 +182,12 @@
     // Three barriers in all: after the sums, after the ballots, after the list.
     // (own text, repeated in istd_mask_stage and pnp6_refine_kernel: as shared functions the sums and the list loop move all three kernels' code — HISTORY.md, round 12)
     int n = 0;                                          // number of candidates = entries of slist
+#ifdef MR_K1_REFIT
+    if (RF_LIST && rf_flag != 0) {                      // workgroup-uniform: the list and its mask are in LDS already; no barrier here — the re-fit's follows
+        n = rf_nfit;
+        if constexpr (!ONE_LIST) { for (int p = tid; p < P; p += NT) smask[p] = (uint8_t)((sball[p >> 6] >> (p & 63)) & 1ull); }
+    } else {                                            // no re-fit record (fewer than four candidates, a failed model): init_mask's bytes, as pnp_uncert_kernel<.., EXT> reads them
+#endif
     if constexpr (EXT) {
         // the external initialiser's inlier mask IS the candidate set (pnp_uncert_cpu.py:43-51: mask[mask] = ransac_mask); no "> 4" rule here
         const uint8_t *gm = a.init_mask + (long long)b * P;
@@ -249,6 +300,9 @@
         }
     }
     __syncthreads();
+#ifdef MR_K1_REFIT
+    }
+#endif
     MR_STAMP(2);
 
     // ---------------------------------------------------------------- stage 2: K0 initialiser (R5)
@@ -264,12 +318,15 @@
         // pnp_uncert_refit_kernel: the external initialiser left its re-fit to this launch (the inlier list IS slist, the tile is here)
         {
             const int *meta = MR_K1_REFIT.w.meta + (long long)b * kEpMeta;
-            const int rflag = meta[EP_M_REFIT];
+            const int rflag = rf_flag;
             init_ok = rflag != 0;
             if (init_ok) {                              // uniform over the workgroup
                 EpCam ecam;
                 ecam.fx = (double)(float)Kall[0]; ecam.fy = (double)(float)Kall[4]; ecam.cx = (double)(float)Kall[2]; ecam.cy = (double)(float)Kall[5];
-                init_ok = ep_refit_object<T, WPO>(tl, slist, n, red, ecam, MR_K1_REFIT.w, MR_K1_REFIT.B, b, (rflag & 2) != 0, wid, lane, init);
+                const double *rprep, *rrec;
+                if constexpr (RF_LIST) { rprep = srf; rrec = srf + 24; }
+                else { rprep = MR_K1_REFIT.w.prep_r + (long long)b * 24; rrec = MR_K1_REFIT.w.cand_r + (long long)b * kEpCandStride; }
+                init_ok = ep_refit_object<T, WPO>(tl, slist, n, red, ecam, rprep, rrec, (rflag & 2) != 0, wid, lane, init, dbg_lm ? dbg_lm - 12 : nullptr);
                 __syncthreads();                        // `red` goes back to the reductions
             }
             if (!init_ok) { init[0] = init[1] = init[2] = init[3] = 0.0; }
