@@ -54,6 +54,7 @@ LATER_HEADERS = {
     'fpn': ('monorun_fpn.h', ('mr_fpn_topdown_forward', 'mr_fpn_topdown_backward')),                                   # section 22
     'backbone': ('monorun_backbone.h', ('mr_bn_act_forward', 'mr_bn_act_backward_workspace_bytes', 'mr_bn_act_backward',
                                         'mr_bn_relu_maxpool_forward')),                                                 # section 23
+    'result3d': ('monorun_result3d.h', ('mr_result3d_nms',)),                                                          # section 24
 }
 
 

@@ -43,19 +43,38 @@ __device__ __forceinline__ float rotated_iou(const NmsBox &a, const NmsBox &b) {
     return ov / fmaxf(a.area + b.area - ov, 1e-8f);
 }
 
-__global__ void __launch_bounds__(256) nms_bev_kernel(const float *boxes, const float *scores, const int *offsets, float thr,
-                                                      long long *keep, int *num_keep) {
-    const int g = blockIdx.x, tid = threadIdx.x;
-    const int off = offsets[g], n = offsets[g + 1] - off;
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int np2 = mr_nms_padded(n);
-    float *skey = (float *)smem;                         // [np2]
-    int *sidx = (int *)(skey + np2);                     // [np2]
-    NmsBox *sbox = (NmsBox *)(sidx + np2);               // [n] in sorted order
+// The box record of one [x1, y1, x2, y2, angle] row: every kernel that runs the NMS builds its boxes here.
+__device__ __forceinline__ NmsBox nms_make_box(float x1, float y1, float x2, float y2, float ang) {
+    NmsBox nb;
+    nb.cx = 0.5f * (x1 + x2); nb.cy = 0.5f * (y1 + y2);
+    const float hw = 0.5f * (x2 - x1), hh = 0.5f * (y2 - y1);
+    float sn, cs; sincosf(ang, &sn, &cs);
+    const float ddx[4] = { -hw, hw, hw, -hw }, ddy[4] = { -hh, -hh, hh, hh };
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { nb.px[c] = nb.cx + ddx[c] * cs + ddy[c] * sn; nb.py[c] = nb.cy - ddx[c] * sn + ddy[c] * cs; }
+    if (hw * hh < 0.0f) {                               // keep the corner order counter-clockwise
+        const float tx = nb.px[1], ty = nb.py[1]; nb.px[1] = nb.px[3]; nb.py[1] = nb.py[3]; nb.px[3] = tx; nb.py[3] = ty;
+    }
+    nb.area = fabsf((x2 - x1) * (y2 - y1));
+    return nb;
+}
+
+// LDS of one group of n boxes (np2 = mr_nms_padded(n)): keys and indices of the sort, the boxes in sorted order, the suppression bits
+// and 16 spare bytes.  include/monorun_result3d.h states the same sum with a fourth array.
+__host__ __device__ constexpr size_t nms_group_lds(int n, int np2) {
+    return (size_t)np2 * 8 + (size_t)n * sizeof(NmsBox) + (size_t)n * ((n + 31) / 32) * 4 + 16;
+}
+
+// One group's NMS over LDS, by the 256 threads of a block (n >= 1, uniform; `scores`: the group's n scores, any address space):
+// the sort into nms_order.inc's order, the boxes (`box_of(j)`: the record of the group's box j), the suppression bits and the
+// wave-synchronous greedy scan.  Thread 0 calls `emit(k, i)` for the k-th kept box, the one at sorted place i (sidx[i]: its index in
+// the group).  Returns the number kept in the first wave (tid < 64) and 0 elsewhere; the caller's LDS writes of the scan are not
+// yet visible to the other waves.
+template <class BoxOf, class Emit>
+__device__ __forceinline__ int nms_group_lds_scan(float *skey, int *sidx, NmsBox *sbox, unsigned *srow, int n, int np2, const float *scores,
+                                                  float thr, int tid, BoxOf box_of, Emit emit) {
     const int nw = (n + 31) >> 5;
-    unsigned *srow = (unsigned *)(sbox + n);             // [n][nw] suppression bits (j > i, IoU > thr)
-    if (n <= 0) { if (tid == 0) num_keep[g] = 0; return; }
-    for (int i = tid; i < np2; i += 256) mr_nms_fill(skey, sidx, i, n, scores + off);
+    for (int i = tid; i < np2; i += 256) mr_nms_fill(skey, sidx, i, n, scores);
     __syncthreads();
     // bitonic sort into the order of nms_order.inc: descending score, ties by ascending index, NaN scores last, padding after them —
     // so the first n places hold a permutation of 0 .. n-1 whatever the scores are
@@ -64,22 +83,7 @@ __global__ void __launch_bounds__(256) nms_bev_kernel(const float *boxes, const 
             for (int i = tid; i < np2; i += 256) mr_nms_step(skey, sidx, i, j, k);
             __syncthreads();
         }
-    for (int i = tid; i < n; i += 256) {
-        const float *b = boxes + (long long)(off + sidx[i]) * 5;
-        const float x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3], ang = b[4];
-        NmsBox nb;
-        nb.cx = 0.5f * (x1 + x2); nb.cy = 0.5f * (y1 + y2);
-        const float hw = 0.5f * (x2 - x1), hh = 0.5f * (y2 - y1);
-        float sn, cs; sincosf(ang, &sn, &cs);
-        const float ddx[4] = { -hw, hw, hw, -hw }, ddy[4] = { -hh, -hh, hh, hh };
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { nb.px[c] = nb.cx + ddx[c] * cs + ddy[c] * sn; nb.py[c] = nb.cy - ddx[c] * sn + ddy[c] * cs; }
-        if (hw * hh < 0.0f) {                               // keep the corner order counter-clockwise
-            const float tx = nb.px[1], ty = nb.py[1]; nb.px[1] = nb.px[3]; nb.py[1] = nb.py[3]; nb.px[3] = tx; nb.py[3] = ty;
-        }
-        nb.area = fabsf((x2 - x1) * (y2 - y1));
-        sbox[i] = nb;
-    }
+    for (int i = tid; i < n; i += 256) sbox[i] = box_of(sidx[i]);
     __syncthreads();
     for (int t = tid; t < n * nw; t += 256) {
         const int i = t / nw, w = t - i * nw;
@@ -92,19 +96,37 @@ __global__ void __launch_bounds__(256) nms_bev_kernel(const float *boxes, const 
         srow[t] = bits;
     }
     __syncthreads();
+    int kept = 0;
     if (tid < 64) {                                          // one wave, wave-synchronous greedy pass
         unsigned removed = 0;                                // lane w holds word w of the removed set (nw <= 16)
-        int kept = 0;
         for (int i = 0; i < n; ++i) {
             const unsigned word = __builtin_amdgcn_readlane(removed, i >> 5);
             if (!((word >> (i & 31)) & 1u)) {
-                if (tid == 0) keep[off + kept] = (long long)sidx[i];
+                if (tid == 0) emit(kept, i);
                 ++kept;
                 if (tid < nw) removed |= srow[i * nw + tid];
             }
         }
-        if (tid == 0) num_keep[g] = kept;
     }
+    return kept;
+}
+
+__global__ void __launch_bounds__(256) nms_bev_kernel(const float *boxes, const float *scores, const int *offsets, float thr,
+                                                      long long *keep, int *num_keep) {
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int off = offsets[g], n = offsets[g + 1] - off;
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int np2 = mr_nms_padded(n);
+    float *skey = (float *)smem;                         // [np2]
+    int *sidx = (int *)(skey + np2);                     // [np2]
+    NmsBox *sbox = (NmsBox *)(sidx + np2);               // [n] in sorted order
+    unsigned *srow = (unsigned *)(sbox + n);             // [n][(n + 31) / 32] suppression bits (j > i, IoU > thr)
+    if (n <= 0) { if (tid == 0) num_keep[g] = 0; return; }
+    const int kept = nms_group_lds_scan(
+        skey, sidx, sbox, srow, n, np2, scores + off, thr, tid,
+        [&](int j) { const float *b = boxes + (long long)(off + j) * 5; return nms_make_box(b[0], b[1], b[2], b[3], b[4]); },
+        [&](int k, int i) { keep[off + k] = (long long)sidx[i]; });
+    if (tid == 0) num_keep[g] = kept;
 }
 
 __global__ void __launch_bounds__(64) spin_kernel(long long ticks) {

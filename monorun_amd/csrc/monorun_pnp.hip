@@ -28,6 +28,7 @@
 #include "monorun_assign.h"
 #include "monorun_fpn.h"
 #include "monorun_backbone.h"
+#include "monorun_result3d.h"
 
 namespace {
 
@@ -119,6 +120,7 @@ constexpr size_t kNocLds = sizeof(double) * (2 * 4 * kRedN + 2 * 40);     // red
 #include "fpn_kernel.inc"
 #include "backbone_kernel.inc"
 #include "consumers_kernel.inc"
+#include "result3d_kernel.inc"
 #include "host_launch.inc"
 
 }  // namespace
@@ -145,6 +147,7 @@ extern "C" {
 #include "assign_abi.inc"
 #include "fpn_abi.inc"
 #include "backbone_abi.inc"
+#include "result3d_abi.inc"
 #include "debug_abi.inc"
 
 }  // extern "C"
