@@ -55,6 +55,7 @@ LATER_HEADERS = {
     'backbone': ('monorun_backbone.h', ('mr_bn_act_forward', 'mr_bn_act_backward_workspace_bytes', 'mr_bn_act_backward',
                                         'mr_bn_relu_maxpool_forward')),                                                 # section 23
     'result3d': ('monorun_result3d.h', ('mr_result3d_nms',)),                                                          # section 24
+    'roi_train': ('monorun_roi_train.h', ('mr_roi_train_positives',)),                                                 # section 25
 }
 
 

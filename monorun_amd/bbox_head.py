@@ -453,7 +453,8 @@ class Shared2FCBBoxHead(nn.Module):
         deltas and clamped to ``img_meta['img_shape']``."""
         assert rois.shape[1] in (4, 5), 'regress_by_class: rois (n, 4) or (n, 5)'
         if not self.reg_class_agnostic:
-            bbox_pred = bbox_pred.reshape(bbox_pred.shape[0], -1, 4).gather(1, label[:, None, None].expand(-1, 1, 4).long()).reshape(-1, 4)
+            groups = bbox_pred.shape[1] // 4                                                        # stated: no rows leave -1 ambiguous
+            bbox_pred = bbox_pred.reshape(bbox_pred.shape[0], groups, 4).gather(1, label[:, None, None].expand(-1, 1, 4).long()).reshape(-1, 4)
         rois5 = rois if rois.shape[1] == 5 else torch.cat((rois.new_zeros(rois.shape[0], 1), rois), dim=1)
         hw = rois.new_tensor([float(img_meta['img_shape'][0]), float(img_meta['img_shape'][1])]).expand(rois.shape[0], 2)
         boxes = decode_torch(rois5, bbox_pred, hw, None, self.target_means, self.target_stds)[:, 0].to(rois.dtype)

@@ -87,16 +87,9 @@ __global__ void __launch_bounds__(kBboxThreads) bbox_head_rank_kernel(const Bbox
         const long long row = first + i;
         const float *roi = a.rois + row * 5, *d = a.reg + row * (a.agnostic ? 4 : 4 * a.C) + (a.agnostic ? 0 : 4 * c);
         const float rx1 = roi[1], ry1 = roi[2], rx2 = roi[3], ry2 = roi[4];
-        const float dx = d[0] * a.std[0] + a.mean[0], dy = d[1] * a.std[1] + a.mean[1];
-        float dw = d[2] * a.std[2] + a.mean[2], dh = d[3] * a.std[3] + a.mean[3];
-        dw = fminf(fmaxf(dw, -a.max_ratio), a.max_ratio);
-        dh = fminf(fmaxf(dh, -a.max_ratio), a.max_ratio);
-        const float px = (rx1 + rx2) * 0.5f, py = (ry1 + ry2) * 0.5f, pw = rx2 - rx1, ph = ry2 - ry1;
-        const float gw = pw * expf(dw), gh = ph * expf(dh);
-        const float gx = px + pw * dx, gy = py + ph * dy;
-        const float img_h = a.img_shape[2 * n], img_w = a.img_shape[2 * n + 1];
-        float x1 = fminf(fmaxf(gx - gw * 0.5f, 0.0f), img_w), y1 = fminf(fmaxf(gy - gh * 0.5f, 0.0f), img_h);
-        float x2 = fminf(fmaxf(gx + gw * 0.5f, 0.0f), img_w), y2 = fminf(fmaxf(gy + gh * 0.5f, 0.0f), img_h);
+        float x1, y1, x2, y2;
+        delta2bbox_clamped(rx1, ry1, rx2, ry2, d[0], d[1], d[2], d[3], a.mean, a.std, a.max_ratio, a.img_shape[2 * n], a.img_shape[2 * n + 1],
+                           x1, y1, x2, y2);
         if (a.scale) {
             const float *f = a.scale + 4 * n;
             x1 = x1 / f[0]; y1 = y1 / f[1]; x2 = x2 / f[2]; y2 = y2 / f[3];

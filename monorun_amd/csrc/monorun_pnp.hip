@@ -29,6 +29,7 @@
 #include "monorun_fpn.h"
 #include "monorun_backbone.h"
 #include "monorun_result3d.h"
+#include "monorun_roi_train.h"
 
 namespace {
 
@@ -121,6 +122,7 @@ constexpr size_t kNocLds = sizeof(double) * (2 * 4 * kRedN + 2 * 40);     // red
 #include "backbone_kernel.inc"
 #include "consumers_kernel.inc"
 #include "result3d_kernel.inc"
+#include "roi_train_kernel.inc"
 #include "host_launch.inc"
 
 }  // namespace
@@ -148,6 +150,7 @@ extern "C" {
 #include "fpn_abi.inc"
 #include "backbone_abi.inc"
 #include "result3d_abi.inc"
+#include "roi_train_abi.inc"
 #include "debug_abi.inc"
 
 }  // extern "C"

@@ -28,6 +28,24 @@ struct ProposalArgs {
     uint8_t *valid;
 };
 
+// mmdet's delta2bbox of one box and its clamp to the image, the ONE copy every kernel that moves a box by deltas calls (this file's decode,
+// bbox_head_kernel.inc's rank launch, roi_train_kernel.inc): d = delta std + mean, dw and dh clamped to +-max_ratio, the centre moved by
+// pw dx, the size scaled by expf(dw), the corners clamped to [0, img_w] x [0, img_h].  Every operation is an fp32 one in this order.
+__device__ __forceinline__ void delta2bbox_clamped(float bx1, float by1, float bx2, float by2, float d0, float d1, float d2, float d3,
+                                                   const float *mean, const float *std, float max_ratio, float img_h, float img_w,
+                                                   float &x1, float &y1, float &x2, float &y2) {
+#pragma clang fp contract(off)
+    const float dx = d0 * std[0] + mean[0], dy = d1 * std[1] + mean[1];
+    float dw = d2 * std[2] + mean[2], dh = d3 * std[3] + mean[3];
+    dw = fminf(fmaxf(dw, -max_ratio), max_ratio);
+    dh = fminf(fmaxf(dh, -max_ratio), max_ratio);
+    const float px = (bx1 + bx2) * 0.5f, py = (by1 + by2) * 0.5f, pw = bx2 - bx1, ph = by2 - by1;
+    const float gw = pw * expf(dw), gh = ph * expf(dh);
+    const float gx = px + pw * dx, gy = py + ph * dy;
+    x1 = fminf(fmaxf(gx - gw * 0.5f, 0.0f), img_w); y1 = fminf(fmaxf(gy - gh * 0.5f, 0.0f), img_h);
+    x2 = fminf(fmaxf(gx + gw * 0.5f, 0.0f), img_w); y2 = fminf(fmaxf(gy + gh * 0.5f, 0.0f), img_h);
+}
+
 // One thread per candidate; blockIdx.y = image * L + level, so the level's row of the table is read with a uniform index.
 __global__ void __launch_bounds__(kPropThreads) proposal_decode_kernel(const ProposalArgs a) {
 #pragma clang fp contract(off)
@@ -48,18 +66,11 @@ __global__ void __launch_bounds__(kPropThreads) proposal_decode_kernel(const Pro
     const int y = cell / lv.W, x = cell - y * lv.W;
     const float logit = lv.cls[((long long)n * a.A + an) * hw + cell];
     const float *rg = lv.reg + ((long long)n * 4 * a.A + 4 * an) * hw + cell;
-    const float dx = rg[0] * a.std[0] + a.mean[0], dy = rg[hw] * a.std[1] + a.mean[1];
-    float dw = rg[2 * (long long)hw] * a.std[2] + a.mean[2], dh = rg[3 * (long long)hw] * a.std[3] + a.mean[3];
-    dw = fminf(fmaxf(dw, -a.max_ratio), a.max_ratio);
-    dh = fminf(fmaxf(dh, -a.max_ratio), a.max_ratio);
     const float sx = (float)x * (float)lv.stride, sy = (float)y * (float)lv.stride;
     const float ax1 = lv.base[an][0] + sx, ay1 = lv.base[an][1] + sy, ax2 = lv.base[an][2] + sx, ay2 = lv.base[an][3] + sy;
-    const float px = (ax1 + ax2) * 0.5f, py = (ay1 + ay2) * 0.5f, pw = ax2 - ax1, ph = ay2 - ay1;
-    const float gw = pw * expf(dw), gh = ph * expf(dh);
-    const float gx = px + pw * dx, gy = py + ph * dy;
-    const float img_h = a.img_shape[2 * n], img_w = a.img_shape[2 * n + 1];
-    const float x1 = fminf(fmaxf(gx - gw * 0.5f, 0.0f), img_w), y1 = fminf(fmaxf(gy - gh * 0.5f, 0.0f), img_h);
-    const float x2 = fminf(fmaxf(gx + gw * 0.5f, 0.0f), img_w), y2 = fminf(fmaxf(gy + gh * 0.5f, 0.0f), img_h);
+    float x1, y1, x2, y2;
+    delta2bbox_clamped(ax1, ay1, ax2, ay2, rg[0], rg[hw], rg[2 * (long long)hw], rg[3 * (long long)hw], a.mean, a.std, a.max_ratio,
+                       a.img_shape[2 * n], a.img_shape[2 * n + 1], x1, y1, x2, y2);
     a.boxes[pos * 4 + 0] = x1; a.boxes[pos * 4 + 1] = y1; a.boxes[pos * 4 + 2] = x2; a.boxes[pos * 4 + 3] = y2;
     a.score[pos] = 1.0f / (1.0f + expf(-logit));
     a.logit[pos] = logit;

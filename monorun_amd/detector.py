@@ -2,8 +2,12 @@
 ``TwoStageDetector``) as a thin class over this package's modules — image in, ``[dict(bbox_results=…, bbox_3d_results=…)]`` out
 (INTEGRATION.md §2).  Sub-modules are given built or as the reference's config dicts (``roi_head.build``); the attribute
 names make the checkpoint prefixes ``backbone.`` / ``neck.`` / ``rpn_head.`` / ``roi_head.``.  ``show_result`` is not provided: it
-needs mmcv's and OpenCV's drawing."""
+needs mmcv's and OpenCV's drawing.  Training side: ``forward_train``, ``_parse_losses`` and ``train_step`` with the
+semantics of mmdet's ``TwoStageDetector`` and ``BaseDetector``."""
+from collections import OrderedDict
+
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 
 from .roi_head import MonoRUnRoIHead, build, cfg_get
@@ -76,9 +80,60 @@ class MonoRUnDetector(nn.Module):
             kwargs['proposals'] = kwargs['proposals'][0]
         return self.simple_test(imgs[0], img_metas[0], **kwargs)
 
+    def forward_train(self, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None, proposals=None, rpn_kwargs=None,
+                      **kwargs):
+        """mmdet's ``TwoStageDetector.forward_train``: ``extract_feat``, the RPN's ``forward_train`` with
+        ``proposal_cfg = train_cfg.rpn_proposal`` (``test_cfg.rpn`` without one), whose losses are merged, then the RoI head's
+        ``forward_train`` on its proposals (on ``proposals`` without an RPN).  ``kwargs``: what the RoI head takes besides (``gt_bboxes_3d``,
+        ``gt_coords_3d``, ``gt_coords_3d_mask``, ``coord_2d``, ``cam_intrinsic``, ``path``, ``generator``, ``keys``); ``rpn_kwargs``: the
+        RPN sampler's ``generator`` / ``keys``.  -> the dict of all losses."""
+        x = self.extract_feat(img)
+        losses = dict()
+        if self.with_rpn:
+            proposal_cfg = cfg_get(self.train_cfg, 'rpn_proposal', cfg_get(self.test_cfg, 'rpn'))
+            rpn_losses, proposal_list = self.rpn_head.forward_train(x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=gt_bboxes_ignore,
+                                                                    proposal_cfg=proposal_cfg, **(rpn_kwargs or {}))
+            losses.update(rpn_losses)
+        else:
+            proposal_list = proposals
+        roi_losses = self.roi_head.forward_train(x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore, gt_masks, **kwargs)
+        losses.update(roi_losses)
+        return losses
+
+    @staticmethod
+    def _parse_losses(losses):
+        """mmdet's ``BaseDetector._parse_losses``: every entry reduced to a scalar (a tensor by its mean, a list of tensors by the sum of
+        their means), ``loss`` the sum of the entries whose key contains ``'loss'``, ``log_vars`` every entry (and ``loss``) as a Python
+        float — averaged over the ranks first where ``torch.distributed`` is initialised.  -> (loss, log_vars)."""
+        log_vars = OrderedDict()
+        for name, value in losses.items():
+            if isinstance(value, torch.Tensor):
+                log_vars[name] = value.mean()
+            elif isinstance(value, (list, tuple)):
+                log_vars[name] = sum(v.mean() for v in value)
+            else:
+                raise TypeError(f'{name} is not a tensor or list of tensors')
+        loss = sum(value for key, value in log_vars.items() if 'loss' in key)
+        log_vars['loss'] = loss
+        for name, value in log_vars.items():
+            if dist.is_available() and dist.is_initialized():
+                value = value.data.clone()
+                dist.all_reduce(value.div_(dist.get_world_size()))
+            log_vars[name] = value.item()
+        return loss, log_vars
+
+    def train_step(self, data, optimizer=None):
+        """mmdet's ``BaseDetector.train_step``: ``data`` the keywords of :meth:`forward` (``img``, ``img_metas`` and the ground truth) ->
+        ``dict(loss, log_vars, num_samples)``; the caller runs ``backward()`` and the optimizer, which is not used here."""
+        losses = self(**data)
+        loss, log_vars = self._parse_losses(losses)
+        return dict(loss=loss, log_vars=log_vars, num_samples=len(data['img_metas']))
+
     def forward(self, img, img_metas, return_loss=True, **kwargs):
         if return_loss:
-            raise NotImplementedError('MonoRUnDetector.forward_train follows MonoRUnRoIHead.forward_train')
+            if self.train_cfg is None:                  # an inference detector stays what it was: it does not train
+                raise NotImplementedError('MonoRUnDetector.forward(return_loss=True): the detector was built without a train_cfg')
+            return self.forward_train(img, img_metas, **kwargs)
         with torch.no_grad():
             return self.forward_test(img, img_metas, **kwargs)
 

@@ -153,7 +153,8 @@ class FCExtractor(nn.Module):
         if self.latent_class_agnostic:
             return t
         inds = torch.arange(len(labels), device=labels.device)
-        return t.view(t.size(0), -1, self.dim_dim + self.latent_channels)[inds, labels]
+        width = self.dim_dim + self.latent_channels
+        return t.view(t.size(0), t.size(1) // width, width)[inds, labels]          # stated: with no rows a -1 is ambiguous
 
     def slice_pred(self, dim_latent_pred, dim_latent_var, labels):
         """-> (dim_pred (n, 3), None, latent_pred (n, latent_channels), None): the class's slice of the prediction."""
