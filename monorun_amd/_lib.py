@@ -56,6 +56,7 @@ LATER_HEADERS = {
                                         'mr_bn_relu_maxpool_forward')),                                                 # section 23
     'result3d': ('monorun_result3d.h', ('mr_result3d_nms',)),                                                          # section 24
     'roi_train': ('monorun_roi_train.h', ('mr_roi_train_positives',)),                                                 # section 25
+    'image': ('monorun_image.h', ('mr_image_prepare',)),                                                               # section 26
 }
 
 

@@ -30,6 +30,7 @@
 #include "monorun_backbone.h"
 #include "monorun_result3d.h"
 #include "monorun_roi_train.h"
+#include "monorun_image.h"
 
 namespace {
 
@@ -123,6 +124,7 @@ constexpr size_t kNocLds = sizeof(double) * (2 * 4 * kRedN + 2 * 40);     // red
 #include "consumers_kernel.inc"
 #include "result3d_kernel.inc"
 #include "roi_train_kernel.inc"
+#include "image_prepare_kernel.inc"
 #include "host_launch.inc"
 
 }  // namespace
@@ -151,6 +153,7 @@ extern "C" {
 #include "backbone_abi.inc"
 #include "result3d_abi.inc"
 #include "roi_train_abi.inc"
+#include "image_abi.inc"
 #include "debug_abi.inc"
 
 }  // extern "C"
